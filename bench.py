@@ -14,7 +14,16 @@ Gaussians in [-1.5,1.5]^3 seen from (0,0,4), fov 50 deg) and resident in HBM bef
 `lane_occupancy` gives the blend kernels' live and valid-pair shares of their lane slots,
 counted on one extra, untimed step.
 
+A plain run does only what the headline figure needs: set-up, the settle and warm-up steps,
+the K timed steps, the result line (metric, value, unit, ms_per_step, ...).  --full adds every
+other leg to that line, each timed apart from the K steps: the unchanged-caller step (before
+them, as a longer warm-up), rotating cameras, the N > 1 exchange profile, per-entry HIP-event times and roofline,
+lane occupancy, the full train step and the CPU baselines.  --dump-outputs DIR writes what the
+last timed step returned to its caller (loss, image, the six parameter gradients) as
+DIR/<name>.npy, float32; the inputs are seeded, so two builds can be compared array by array.
+
 Usage:  python bench.py [--gpus N] [--steps K] [--warmup W] [--config headline|c2|c3|c4|c5]
+                        [--full] [--dump-outputs DIR]
 (N > 1 under torch.distributed.run, one process per GPU, backend nccl = RCCL.)
 """
 from __future__ import annotations
@@ -630,16 +639,71 @@ def train_roofline(train_step, steps, barrier, ab, N, I, P, T, K, world, trainer
     return out
 
 
+DUMP_BUDGET_BYTES = 48 << 20  # --dump-outputs: all arrays together (float32)
+
+
+def step_outputs(last, scene, fwd_only):
+    """What the timed step handed its caller, by name: the loss and the raw image of the last
+    view rendered, and the parameter gradients the step left in .grad (summed over the views and
+    ranks); forward only: the image (and alpha where the render returns it)."""
+    arrays = {}
+    if fwd_only:
+        out = last
+    elif isinstance(last, tuple):
+        arrays["loss"], out = last
+    else:  # several views per rank: the summed loss
+        arrays["loss"], out = last, {}
+    for k in ("rgb", "accumulation"):
+        if out.get(k) is not None:
+            arrays[k] = out[k]
+    if not fwd_only:
+        for name, p in zip(("means", "scales", "quats", "opacities", "features_dc",
+                            "features_rest"), scene.params()):
+            if p.grad is not None:
+                arrays["grad_" + name] = p.grad
+    return arrays
+
+
+def dump_outputs(directory, arrays, budget=DUMP_BUDGET_BYTES, seed=0):
+    """Write each array as directory/<name>.npy in float32.  The arrays share `budget` bytes,
+    smallest first, each taking at most an equal share of what is left; an array over its share
+    is cut to a seeded random sample of its leading-axis rows, in ascending row order -- the same
+    rows for the same shapes, so two runs' files compare row for row."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    rng = np.random.default_rng(seed)
+    todo = sorted(arrays.items(), key=lambda kv: kv[1].numel())
+    for i, (name, t) in enumerate(todo):
+        t = t.detach().to(torch.float32)
+        share = budget // (len(todo) - i)
+        if t.numel() * 4 > share and t.dim() > 0:
+            rows = max(1, share // (4 * max(1, t[0].numel())))
+            idx = np.sort(rng.choice(t.shape[0], size=rows, replace=False))
+            t = t[torch.from_numpy(idx).to(t.device)]
+        a = t.contiguous().cpu().numpy()
+        np.save(os.path.join(directory, name + ".npy"), a)
+        budget -= a.nbytes
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--config", default="headline", choices=sorted(CONFIGS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--train-steps", type=int, default=None)
+    ap.add_argument("--full", action="store_true",
+                    help="also run every other leg, each timed apart (unchanged caller, "
+                         "rotating cameras, exchange profile, per-entry times and roofline, lane "
+                         "occupancy, train step, CPU baselines) and report them in the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (loss, image, parameter "
+                         "gradients) as DIR/<name>.npy, float32, at most 48 MiB in all (larger "
+                         "arrays: a fixed seeded sample of rows)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU legs")
+    ap.add_argument("--train-steps", type=int, default=None,
+                    help="(--full) steps of the train leg (default: --steps)")
     ap.add_argument("--no-lane-occupancy", action="store_true",
-                    help="skip the counted extra step (profiler runs: keeps the counting "
+                    help="(--full) skip the counted extra step (profiler runs: keeps the counting "
                          "kernels out of the PMC and kernel-trace summaries)")
     ap.add_argument("--forward-only", action="store_true",
                     help="time the render without backward (default for config c2)")
@@ -651,8 +715,10 @@ def main():
                     help="fused: the caller's activations inside the HIP kernels (default); "
                          "caller: gc_model.py's torch glue around the gsplat API")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
-    world = int(os.environ.get("WORLD_SIZE", "1"))
+    world =int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     # one GPU per rank (RCCL); BENCH_DIST_BACKEND=gloo lets a one-GPU box rehearse the N > 1
@@ -678,7 +744,8 @@ def main():
     bg = torch.zeros(3, device=dev)
     trainer = TrainStep(scene, sh_degree=deg, world_size=world, loss="l1",
                         render_mode=args.render)
-    caller = TrainStep(scene, sh_degree=deg, world_size=world, loss="l1", render_mode="caller")
+    caller = TrainStep(scene, sh_degree=deg, world_size=world, loss="l1",
+                       render_mode="caller") if args.full else None
 
     fwd_only = args.forward_only or args.config in FORWARD_ONLY
 
@@ -689,24 +756,24 @@ def main():
 
     def step_views(t, cams):
         t.zero_grad()
-        t.forward_backward_views(cams, gts[:len(cams)], bg)
+        total = t.forward_backward_views(cams, gts[:len(cams)], bg)
         t.sync_grads()
+        return total
 
     def step_eager(t=trainer, c=None):
+        """One step; returns what its caller receives (--dump-outputs, step_outputs)."""
         c = cam if c is None else c
         if V > 1 and not fwd_only and t.render_mode == "fused":
-            step_views(t, [c] + extra)
-            return
+            return step_views(t, [c] + extra)
         if fwd_only:
             with torch.no_grad():
                 if t.render_mode == "fused":
-                    render_fused(scene, c, deg, bg)
-                else:
-                    render(scene, c, deg, bg)
-            return
+                    return render_fused(scene, c, deg, bg)
+                return render(scene, c, deg, bg)
         t.zero_grad()
-        t.forward_backward(c, gt, bg)
+        res = t.forward_backward(c, gt, bg)
         t.sync_grads()
+        return res
 
     step = step_eager
 
@@ -736,18 +803,21 @@ def main():
     for _ in range(SETTLE_STEPS):
         step()
     barrier()
-    # the same step through the unchanged caller's torch glue (gc_model.py as it runs on the
-    # gsplat drop-in), for comparison
-    for _ in range(max(args.warmup // 2, 1)):
-        step(caller)
-    caller_value = world * H * W * args.steps / timed(lambda: step(caller), args.steps) / 1e6
+    caller_value = None
+    if args.full:
+        # the same step through the unchanged caller's torch glue (gc_model.py as it runs on
+        # the gsplat drop-in), for comparison
+        for _ in range(max(args.warmup // 2, 1)):
+            step(caller)
+        caller_value = world * H * W * args.steps / timed(lambda: step(caller), args.steps) / 1e6
 
     for _ in range(args.warmup):
         step()
     barrier()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
+    for _ in range(args.steps - 1):
         step()
+    last = step()  # the last timed step's outputs, kept for --dump-outputs
     barrier()
     dt = time.perf_counter() - t0
     if world > 1:
@@ -756,6 +826,48 @@ def main():
         dt = float(t.item())
     ms_per_step = dt / args.steps * 1e3
     value = world * V * H * W * args.steps / dt / 1e6
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, step_outputs(last, scene, fwd_only))
+    del last
+    T = cam.tile_bounds[0] * cam.tile_bounds[1]
+    line = {
+        "metric": ("Mpixels/s fwd+bwd and train iters/s, 1M Gaussians @ 1080^2"
+                   if not fwd_only else "Mpixels/s forward and train iters/s"),
+        "value": round(value, 2),
+        "unit": "Mpixels/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "settle_steps": SETTLE_STEPS,
+        "ms_per_step": round(ms_per_step, 4),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "fp32",
+        "data": ("synthetic (random-Gaussian scene per SURVEY.md §8d; random-init params)"
+                 if real is None else f"{real} cameras + seed cloud (tests/golden); "
+                 "random-init Gaussians around the seeds; synthetic GT"),
+        "config": {
+            "workload": desc,
+            "num_gaussians": N,
+            "tiles": T,
+            "image": [H, W],
+            "sh_degree": deg,
+            "views_per_gpu_per_step": V,
+            "parallelism": f"dp{world} ({V} view/GPU; SH-coefficient grads by RCCL "
+                           f"all-gather of each view's colour-gradient record (sparse: "
+                           f"visible Gaussians only, when smaller) + multi-view SH backward, "
+                           f"other {N * 11 * 4} B of grads RCCL all-reduced)" if world > 1
+                           else "dp1",
+        },
+        "render": args.render,
+    }
+    if not args.full:  # a plain run: the headline figure alone
+        if rank == 0:
+            print(json.dumps(line), flush=True)
+        if world > 1:
+            dist.destroy_process_group()
+        return
     value_2v = None
     if world > 1 and V == 1 and not fwd_only and args.render == "fused":
         # the same job with two views per rank per step (exchange.py: the first view's record
@@ -908,39 +1020,8 @@ def main():
         cpu = cpu_baseline(scene, cam_cpu, deg, backward=not fwd_only)
 
     if rank == 0:
-        line = {
-            "metric": ("Mpixels/s fwd+bwd and train iters/s, 1M Gaussians @ 1080^2"
-                       if not fwd_only else "Mpixels/s forward and train iters/s"),
-            "value": round(value, 2),
-            "unit": "Mpixels/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "settle_steps": SETTLE_STEPS,
-            "ms_per_step": round(ms_per_step, 4),
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "fp32",
-            "data": ("synthetic (random-Gaussian scene per SURVEY.md §8d; random-init params)"
-                     if real is None else f"{real} cameras + seed cloud (tests/golden); "
-                     "random-init Gaussians around the seeds; synthetic GT"),
-            "config": {
-                "workload": desc,
-                "num_gaussians": N,
-                "num_visible": nvis,
-                "num_intersects": I,
-                "tiles": T,
-                "image": [H, W],
-                "sh_degree": deg,
-                "views_per_gpu_per_step": V,
-                "parallelism": f"dp{world} ({V} view/GPU; SH-coefficient grads by RCCL "
-                               f"all-gather of each view's colour-gradient record (sparse: "
-                               f"visible Gaussians only, when smaller) + multi-view SH backward, "
-                               f"other {N * 11 * 4} B of grads RCCL all-reduced)" if world > 1
-                               else "dp1",
-            },
-            "render": args.render,
+        line["config"].update({"num_visible": nvis, "num_intersects": I})
+        line.update({
             "exchange": exch,
             "value_2_views_per_gpu": value_2v,
             "value_rotating_cameras": rotating["value"],
@@ -955,7 +1036,7 @@ def main():
             "kernels": kernels,
             "kernels_timing": kernels_timing,
             "cpu_baseline": cpu,
-        }
+        })
         print(json.dumps(line), flush=True)
     if world > 1:
         dist.destroy_process_group()

@@ -59,3 +59,28 @@ def test_train_parts():
     assert bench.train_part("gsplat_exchange_pack_sparse").startswith("exchange")
     assert bench.train_part("gsplat_bin_speculative") == "render"
     assert bench.train_part("gsplat_fused_preprocess_backward_adam").startswith("geometry")
+
+
+def test_dump_outputs_sample_is_fixed_and_within_budget(tmp_path):
+    """bench.py --dump-outputs: float32 files, small arrays whole, an array over its share cut
+    to the same ascending seeded rows on every call, the files together within the budget."""
+    import numpy as np
+    import torch
+    arrays = {"loss": torch.tensor(0.25, dtype=torch.float64),
+              "rgb": torch.arange(7 * 5 * 3, dtype=torch.float32).reshape(7, 5, 3),
+              "grad_big": torch.arange(1000 * 6, dtype=torch.float32).reshape(1000, 6)}
+    budget = 4096
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), arrays, budget=budget)
+    got = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in arrays}
+    assert all(a.dtype == np.float32 for a in got.values())
+    assert got["loss"].shape == () and got["loss"] == np.float32(0.25)
+    np.testing.assert_array_equal(got["rgb"], arrays["rgb"].numpy())
+    big = got["grad_big"]
+    assert 1 < big.shape[0] < 1000 and big.shape[1:] == (6,)
+    rows = (big[:, 0] / 6).astype(np.int64)  # row r starts at 6 r
+    assert (np.diff(rows) > 0).all()
+    np.testing.assert_array_equal(big, arrays["grad_big"].numpy()[rows])
+    assert sum(a.nbytes for a in got.values()) <= budget
+    for n in arrays:
+        np.testing.assert_array_equal(got[n], np.load(tmp_path / "b" / f"{n}.npy"))

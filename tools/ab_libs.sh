@@ -6,7 +6,7 @@ mkdir -p gpurun_out
 for r in $(seq ${REPS:-2}); do
   for L in ${LIBS:-ab/libA.so ab/libB.so}; do
     echo "== $L rep $r"
-    GSPLAT_MI355X_LIB=$L timeout -k 10 300 python3 bench.py --config ${CONFIG:-headline} \
+    GSPLAT_MI355X_LIB=$L timeout -k 10 300 python3 bench.py --full --config ${CONFIG:-headline} \
       --steps 50 --warmup 10 --no-cpu-baseline --train-steps ${TRAIN_STEPS:-5} > gpurun_out/ab.log 2>&1 || exit $?
     python3 - <<'PY'
 import json

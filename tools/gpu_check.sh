@@ -25,7 +25,7 @@ if [[ $STEPS == *smoke* ]]; then
   ok $rc || exit $rc
 fi
 if [[ $STEPS == *bench* ]]; then
-  step bench 900 python bench.py ${BENCH_ARGS:-}; rc=$?
+  step bench 900 python bench.py --full ${BENCH_ARGS:-}; rc=$?
   ok $rc || exit $rc
 fi
 exit 0

@@ -26,7 +26,7 @@ for r in $(seq ${REPS:-1}); do
 for c in ${CFGS:-}; do
   for ab in ${AB:-cur:X=0}; do
     name=${ab%%:*}; envs=${ab#*:}
-    env $(echo $envs | tr ',' ' ') timeout -k 10 300 python3 bench.py --config $c --steps ${STEPS:-50} --warmup 10 \
+    env $(echo $envs | tr ',' ' ') timeout -k 10 300 python3 bench.py --full --config $c --steps ${STEPS:-50} --warmup 10 \
       --no-cpu-baseline --no-lane-occupancy --train-steps ${TRAIN_STEPS:-10} > $O/b_${c}_${name}_$r.json 2>> $L || exit $?
     python3 - "$c" "$name" "$O/b_${c}_${name}_$r.json" >> $L <<'PY'
 import json, sys
@@ -40,15 +40,15 @@ done
 if [ -n "$GLOO2" ]; then
   # the N > 1 bench path rehearsed on one GPU: two ranks, gloo carrying the collectives
   BENCH_DIST_BACKEND=gloo timeout -k 10 600 python3 -m torch.distributed.run --nnodes=1 \
-    --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 \
+    --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 bench.py --full --gpus 2 \
     --config ${GLOO2_CFG:-headline} --steps 10 --warmup 3 --no-cpu-baseline --no-lane-occupancy \
     --train-steps 2 > $O/gloo2_${GLOO2_CFG:-headline}.json 2>> $L || exit $?
   tail -n 1 $O/gloo2_${GLOO2_CFG:-headline}.json >> $L
 fi
 if [ -n "$TIMELINE" ]; then
   for c in $TIMELINE; do
-    timeout -k 10 240 rocprofv3 --kernel-trace -d gpurun_out/tl_$c -o run -- python3 bench.py --config $c --steps 6 --warmup 3 --no-cpu-baseline --no-lane-occupancy --train-steps 0 > $O/tl_bench_$c.log 2>&1 || exit $?
-    python3 tools/step_timeline.py gpurun_out/tl_$c/run_results.db ${TL_MARK:-fused_fwd_proj_kernel} 5 > $O/timeline_$c.txt || exit $?
-    rm -rf gpurun_out/tl_$c
+    timeout -k 10 240 rocprofv3 --kernel-trace -d $O/tl_$c -o run -- python3 bench.py --full --config $c --steps 6 --warmup 3 --no-cpu-baseline --no-lane-occupancy --train-steps 0 > $O/tl_bench_$c.log 2>&1 || exit $?
+    python3 tools/step_timeline.py $O/tl_$c/run_results.db ${TL_MARK:-fused_fwd_proj_kernel} 5 > $O/timeline_$c.txt || exit $?
+    rm -rf $O/tl_$c
   done
 fi

@@ -8,7 +8,7 @@ O=gpurun_out/${ROUND:-prof}
 mkdir -p $O
 for c in ${CFGS:-headline}; do
   env ${ENVS:-X=0} timeout -k 10 240 rocprofv3 --kernel-trace -d gpurun_out/pf_$c -o run -- \
-    python3 bench.py --config $c --steps ${STEPS:-10} --warmup 3 --no-cpu-baseline \
+    python3 bench.py --full --config $c --steps ${STEPS:-10} --warmup 3 --no-cpu-baseline \
     --no-lane-occupancy --train-steps 0 > $O/pf_$c.log 2>&1 || exit $?
   python3 tools/rocpd_stats.py gpurun_out/pf_$c/run_results.db $O/ks_$c.csv || exit $?
   rm -rf gpurun_out/pf_$c
