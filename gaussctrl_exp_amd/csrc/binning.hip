@@ -1846,10 +1846,11 @@ __global__ __launch_bounds__(NT) void bk_sort_kernel(int nbk, uint32_t lo, uint3
       }
       if (phase == 1) break;
       // in key order now: equal neighbours are id ties, which need the id digits first
-      uint32_t tie = 0;
+      // (no key digit varies: every key is equal, and no pass has written sm.key yet)
+      uint32_t tie = keymask == 0 ? 1u : 0u;
 #pragma unroll
       for (int r = 0; r < ITEMS; ++r) {
-        if (r >= R) break;
+        if (r >= R || keymask == 0) break;
         const int i = wave * R * 64 + r * 64 + lane;
         if (i > 0 && i < (int)L && sm.key[i - 1] == k[r]) tie = 1;
       }
