@@ -113,6 +113,25 @@ class FusedAdam:
             out.append((p, st["exp_avg"], st["exp_avg_sq"], float(g["lr"])))
         return out
 
+    def replace(self, old, new, exp_avg, exp_avg_sq):
+        """Swap the group holding parameter `old` over to `new` with the given moments (density
+        control: density.refine changes the number of rows).  The step count -- shared by every
+        group -- and the group's settings stay; fused_spec / next_step_groups / step then hand
+        out the new buffers."""
+        for t in (new, exp_avg, exp_avg_sq):
+            if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
+                raise RuntimeError("FusedAdam.replace: contiguous fp32 ROCm tensors only "
+                                   "(no CPU path)")
+        if exp_avg.shape != new.shape or exp_avg_sq.shape != new.shape:
+            raise ValueError("FusedAdam.replace: the moments must have the parameter's shape")
+        for g in self.param_groups:
+            if g["params"][0] is old:
+                g["params"] = [new]
+                self.state.pop(old, None)
+                self.state[new] = {"exp_avg": exp_avg, "exp_avg_sq": exp_avg_sq}
+                return
+        raise ValueError("FusedAdam.replace: parameter not managed by this optimiser")
+
     def zero_grad(self, set_to_none: bool = True):
         for g in self.param_groups:
             p = g["params"][0]

@@ -408,6 +408,16 @@ def _note_key_range(key, host):
     _KEY_VARY[key] = _KEY_VARY.get(key, 0) | (int(host[3]) & 0xFFFFFFFF)
 
 
+def forget_num_points(n: int):
+    """Drop what the frame shapes of scenes with `n` Gaussians have learned (the emission
+    capacity, its window, the depth keys' varying bits): density control has changed the
+    trained scene's N, and its shapes at the old N will not come back.  A shape at the new N
+    starts from the first-call path by itself -- every table is keyed by N."""
+    for table in (_EMIT_CAP, _CAP_WINDOW, _KEY_VARY):
+        for key in [k for k in table if k[1] == n]:
+            del table[key]
+
+
 def _assumed_constant(key) -> int:
     v = _KEY_VARY.get(key)
     return 0 if v is None or not ASSUME_KEY_RANGE else (~v) & 0xFFFFFFFF

@@ -138,7 +138,8 @@ class TrainStep:
     def __init__(self, scene: GaussianScene, sh_degree: int = 3, world_size: int = 1,
                  loss: str = "splatfacto", group=None, api=None,
                  grad_exchange: str = "sh_views", render_mode: str = "caller",
-                 fuse_adam: bool = True, sparse_exchange: str = "auto"):
+                 fuse_adam: bool = True, sparse_exchange: str = "auto",
+                 density=None, density_seed: int = 0):
         if render_mode not in ("caller", "fused"):
             raise ValueError(f"render_mode must be 'caller' or 'fused', not {render_mode}")
         if render_mode == "fused" and (api is not None or not scene.means.is_cuda):
@@ -183,6 +184,77 @@ class TrainStep:
         else:  # CPU-oracle emulation (tests): torch's Adam, same semantics
             self.opt = torch.optim.Adam(groups, eps=1e-15, foreach=True)
         self.step_count = 0
+        # density control (density.DensityConfig; None: the set of Gaussians never changes and
+        # nothing below runs): splatfacto's after_train statistics after every optimiser step,
+        # its refinement_after every refine_every steps (_after_step)
+        self.density = density
+        self.last_refine = None  # the latest refinement's report (density.refine)
+        self._views = []  # this step's (render output, H, W), for the statistics
+        self._frame = None
+        if density is not None:
+            if not isinstance(self.opt, FusedAdamType()):
+                raise ValueError("TrainStep(density=...) runs the MI355X kernels only (no api "
+                                 "override, ROCm tensors)")
+            from .density import DensityStats
+            self.density_stats = DensityStats(scene.num_points, scene.means.device)
+            # the split samples: a CPU generator, seeded alike on every rank, so that every
+            # rank refines to identical tensors
+            self.density_generator = torch.Generator().manual_seed(int(density_seed))
+
+    def rebind(self, scene: GaussianScene):
+        """Train `scene` from now on: its six tensors are already the optimiser's parameters
+        (density.refine -> FusedAdam.replace).  Everything that holds the parameters by
+        identity follows; the frame-shape state of rasterize.py (_EMIT_CAP, _CAP_WINDOW,
+        _KEY_VARY) is keyed by the number of Gaussians, so a changed N starts from its first-call
+        path by itself and the old N's entries are dropped; its binning cache holds its inputs
+        by weak reference and fused._SIDE is per device: neither depends on N."""
+        old_n = self.scene.num_points
+        self.scene = scene.requires_grad_()
+        self.params = scene.params()
+        if scene.num_points != old_n:
+            from .rasterize import forget_num_points
+            forget_num_points(old_n)
+        if self.grad_sync is not None:
+            self.grad_sync.params = list(self.params)
+            self.grad_sync.sh_ids = {id(scene.features_dc), id(scene.features_rest)}
+        if self.sh_exchange is not None:
+            self.sh_exchange.reset()
+
+    @torch.no_grad()
+    def _after_step(self, step: int):
+        """splatfacto's after_train and refinement_after for iteration `step` (0-based), which
+        has just taken its optimiser step."""
+        cfg, stats = self.density, self.density_stats
+        views, self._views = self._views, []
+        if cfg.accumulates(step):
+            for out, H, W in views:
+                if "xys_grad" in out:  # the fused render: v_xy from the gradient records
+                    v_xy = out["xys_grad"]()
+                else:  # the caller's path: xys.grad (scene.render retains it)
+                    v_xy = out["xys"].grad
+                if v_xy is None:  # nothing was visible: no gradient reached the centres
+                    v_xy = torch.zeros_like(out["xys"])
+                stats.accumulate(v_xy, out["radii"], H, W)
+        if cfg.should_refine(step):
+            self._refine(step, views[-1][1:] if views else self._frame)
+
+    @torch.no_grad()
+    def _refine(self, step: int, frame):
+        """splatfacto's refinement_after: the scene, the optimiser state and everything bound to
+        the parameters move over to the refined tensors."""
+        cfg, stats = self.density, self.density_stats
+        if self.world_size > 1 and not stats.fresh:
+            # each rank saw its own views: the ranks' sums and maxima
+            dist.all_reduce(stats.grad_norm, op=dist.ReduceOp.SUM, group=self.group)
+            dist.all_reduce(stats.vis_counts, op=dist.ReduceOp.SUM, group=self.group)
+            dist.all_reduce(stats.max_2Dsize, op=dist.ReduceOp.MAX, group=self.group)
+        from .density import refine
+        H, W = frame
+        for p in self.params:
+            p.grad = None
+        scene, self.last_refine = refine(self.scene, self.opt, stats, cfg, step, H, W,
+                                         generator=self.density_generator)
+        self.rebind(scene)
 
     def _xyz_lr(self):
         t = min(self.step_count / XYZ_MAX_STEPS, 1.0)
@@ -242,6 +314,9 @@ class TrainStep:
                 out = self._render(cam, background, gt=gt)
         else:
             out = self._render(cam, background, adam=adam, gt=gt)
+        if self.density is not None:
+            self._frame = (cam.height, cam.width)
+            self._views.append((out, cam.height, cam.width))
         loss = out.get("loss")
         direct = out.get("backward")
         if direct is not None:  # the fused render's direct step (no autograd graph)
@@ -319,6 +394,8 @@ class TrainStep:
             spec = self.opt.fused_spec(self.params)
             loss, out = self.forward_backward(cam, gt, background, adam=spec)
             self.step_count += 1
+            if self.density is not None:
+                self._after_step(self.step_count - 1)
             return loss
         self.zero_grad()
         xc = self.sh_exchange
@@ -336,6 +413,7 @@ class TrainStep:
             loss, out = self.forward_backward(cam, gt, background)
         if not optimizer:
             self.sync_grads()
+            self._views = []
             return loss
         gs = self.grad_sync
         if gs is not None and xc is not None and xc.adam_applied:
@@ -343,6 +421,8 @@ class TrainStep:
             gs.wait()
             self.opt.step(names=[n for n in PARAM_NAMES if n not in SH_GROUPS])
             self.step_count += 1
+            if self.density is not None:
+                self._after_step(self.step_count - 1)
             return loss
         if xc is not None:
             xc.adam = None  # (not consumed: the caller path / degree-0 steps sum gradients)
@@ -357,4 +437,6 @@ class TrainStep:
             self.sync_grads()
             self.opt.step()
         self.step_count += 1
+        if self.density is not None:
+            self._after_step(self.step_count - 1)
         return loss

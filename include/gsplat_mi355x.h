@@ -637,6 +637,79 @@ int gsplat_adam_step(int num_tensors, float *const *params, const float *const *
                      const float *lrs, int step, float beta1, float beta2, float eps,
                      void *stream);
 
+/* ---- density control (splatfacto's refinement) --------------------------------------------
+ * nerfstudio 1.0.0 SplatfactoModel's after_train / refinement_after callbacks, which the
+ * reference's training loop runs with splatfacto's defaults: per-step refinement statistics,
+ * and every refine_every steps the cull / split / duplicate of the Gaussians with the matching
+ * edit of the Adam moments.  The semantics are restated from memory of splatfacto (DESIGN.md
+ * §4 "Density control"; parity with nerfstudio's code is unpinned).  All tensors fp32,
+ * contiguous, on the device; scene.PARAM_NAMES order (means [N,3], scales [N,3], quats [N,4],
+ * opacities [N,1], features_dc [N,3], features_rest [N,K-1,3]) wherever six pointers are taken.
+ *
+ * gsplat_density_accumulate: one launch, no host sync.  v_xy [N,2] (the rasterizer's gradient
+ *   of the projected centres, splatfacto's xys.grad), radii [N] int32, D = max(H, W),
+ *   g = |v_xy|, vis = radii > 0.  first != 0 (the first call after a reset; the statistics
+ *   need no initialisation): grad_norm = g and vis_counts = 1 for EVERY row (splatfacto's
+ *   behaviour), max_2dsize = 0 and then the max update.  Otherwise, where vis: vis_counts += 1,
+ *   grad_norm += g.  Every call, where vis: max_2dsize = max(max_2dsize, radii / (float)D).
+ *
+ * gsplat_density_plan: the per-row decisions and the output layout of one refinement.
+ *   mode 0: nothing is deleted (every row kept, no inputs read); mode 2 (cull only): a row goes
+ *   if low | (toobig_on & big_scale); mode 1 (densify, then cull the concatenated set):
+ *     size = max(exp(scales)), low = sigmoid(opacity) < cull_alpha_thresh,
+ *     big_scale = size > cull_scale_thresh, big_screen = max_2dsize > cull_screen_size,
+ *     avg = grad_norm / vis_counts * 0.5 * max_dim, high = avg > densify_grad_thresh,
+ *     split = (size > densify_size_thresh | (screen_on & max_2dsize > split_screen_size)) & high,
+ *     dup = (size <= densify_size_thresh) & high;
+ *     an original goes if split | low | (toobig_on & (big_scale | (screen_on & big_screen))),
+ *     a split row's children (all n_split_samples of them) go if low | (toobig_on & the child's
+ *     size, max(exp(log(exp(scales) / 1.6))), > cull_scale_thresh), a duplicate goes if
+ *     low | (toobig_on & big_scale).
+ *   toobig_on / screen_on: the schedule's step > reset_interval / step < stop_screen_size_at,
+ *   decided by the caller.  grad_norm / vis_counts (and max_2dsize with screen_on) are read in
+ *   mode 1 only and may be NULL otherwise.
+ *   plan: int32 [GSPLAT_DENSITY_PLAN_WORDS(N)]: totals {K kept originals, S kept split parents,
+ *   Dn kept duplicates, new_N = K + n_split_samples S + Dn}, flags [N] (bit 0 kept original,
+ *   bit 1 kept split parent, bit 2 kept duplicate), the three counters' exclusive prefix sums
+ *   [N] each, scratch.  The scans are reduce-then-scan over three launches (no workgroup waits
+ *   on another).  The host reads the totals (one sync per refinement) to allocate the outputs.
+ *   Fails if N (2 + n_split_samples) exceeds int32.
+ *
+ * gsplat_density_apply: writes the new_N rows of the six parameters and their twelve Adam
+ *   moments (exp_avg, exp_avg_sq) from a plan: params / exp_avgs / exp_avg_sqs / out_*: HOST
+ *   arrays of six device pointers (features_rest's may be NULL with sh_bases 1: nothing is
+ *   launched for it).  Output order: the kept originals in row order; for sample
+ *   s = 0 .. n_split_samples-1 the children of the kept split parents in parent order (the
+ *   child of the parent of rank r at row K + s S + r); the duplicates in row order (rank d at
+ *   K + n_split_samples S + d).  Kept originals and duplicates are copied bit for bit; a child
+ *   has mean = R(q / |q|) (exp(scales) * z[s, parent]) + mean, scales = log(exp(scales) / 1.6)
+ *   and the parent's other four rows bit for bit.  z [n_split_samples, N, 3]: standard normal
+ *   samples, indexed by ORIGINAL row.  Kept originals keep their moments bit for bit; children
+ *   and duplicates get zeros.  reset_opacity != 0: afterwards opacities = min(opacities,
+ *   opacity_cap) (splatfacto: logit(2 cull_alpha_thresh)) and the opacity moments are zeroed.
+ *   src_rows: int32 [new_N] scratch.  new_N must be the plan's totals[3]; every output index is
+ *   checked against new_N (and the plan's own count).  N == 0 or new_N == 0: nothing is
+ *   launched.  One scatter launch (the source map) and one gather launch over all 18 outputs. */
+#define GSPLAT_DENSITY_PLAN_ROWS 256
+#define GSPLAT_DENSITY_PLAN_WORDS(n) \
+  (4 + 4 * (n) + 3 * (((n) + GSPLAT_DENSITY_PLAN_ROWS - 1) / GSPLAT_DENSITY_PLAN_ROWS))
+int gsplat_density_accumulate(int num_points, const float *v_xy, const int32_t *radii,
+                              int img_height, int img_width, int first, float *grad_norm,
+                              float *vis_counts, float *max_2dsize, void *stream);
+int gsplat_density_plan(int num_points, const float *scales, const float *opacities,
+                        const float *grad_norm, const float *vis_counts,
+                        const float *max_2dsize, int mode, int toobig_on, int screen_on,
+                        int n_split_samples, int max_dim, float cull_alpha_thresh,
+                        float cull_scale_thresh, float cull_screen_size,
+                        float densify_grad_thresh, float densify_size_thresh,
+                        float split_screen_size, int32_t *plan, size_t plan_bytes, void *stream);
+int gsplat_density_apply(int num_points, int new_points, int sh_bases, int n_split_samples,
+                         const int32_t *plan, size_t plan_bytes, const float *const *params,
+                         const float *const *exp_avgs, const float *const *exp_avg_sqs,
+                         const float *z, float *const *out_params, float *const *out_exp_avgs,
+                         float *const *out_exp_avg_sqs, int32_t *src_rows, int reset_opacity,
+                         float opacity_cap, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
