@@ -794,6 +794,11 @@ int radix_sort_pairs(K *ka, uint32_t *va, K *kb, uint32_t *vb, K *kout, uint32_t
          "hipMemcpyAsync");
     return 0;
   }
+  if (p.items == 8 && p.width != 8) {  // (os_pass_kernel of 8 items exists for 8-bit digits only)
+    set_error("radix_sort_pairs: a plan of 8 items per thread needs 8-bit digits (width %d)",
+              p.width);
+    return 1;
+  }
   uint32_t *counts = rts_tile_counts(ws);                      // tile digit counts
   uint32_t *rowtot = counts + (size_t)p.nblocks * p.radix;     // their row totals
   uint32_t *kept = sort_kept_word(ws);
@@ -2105,7 +2110,8 @@ void ts_launch(int n, const Phase1 &p1, void *ws2, int32_t *ids, int32_t *tile_b
     const EcMatrix em = ec_matrix(ws2, cap, T, n);
     ec.counts = em.counts;
     ec.width = em.plan.width;
-    ec.shift = em.plan.items == 16 ? 12 : 10;  // (TPB * items slots per sort tile)
+    // log2 of the TPB * items slots per sort tile (items is a power of two)
+    ec.shift = 31 - __builtin_clz((unsigned)(TPB * em.plan.items));
     ec.nblocks = em.plan.nblocks;
   }
   const int nb = (int)cdiv(n, SC_TILE);

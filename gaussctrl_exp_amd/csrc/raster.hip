@@ -19,7 +19,7 @@
 //    cull keeps a rounding margin, so results are unchanged bit for bit.
 //  * Forward (raster_fwd3u_kernel): two staged Gaussians per iteration -- their sigma /
 //    exp / alpha are independent; the blend is applied in list order, branch-free.
-//  * Backward (shipped: raster_bwd3p_kernel<1>, 16x8 strips, 2 pixels per lane): the lane's
+//  * Backward, full frames (raster_bwd3p_kernel, 16x8 strips, 2 pixels per lane): the lane's
 //    two pixels are a float2 pair blended branch-free; per Gaussian the lane folds them into
 //    9 partial sums (sigma-gradient moments, colour and opacity terms), the wave
 //    reduce-scatters the 9 sums (common.h reduce_rec: permlane32/16 swaps + 3 DPP steps) so
@@ -141,13 +141,12 @@ struct DetLease {
     if (s && s->done) note(hipEventRecord(s->done, st), "hipEventRecord");
   }
 };
-constexpr int FWD_PXL = 1;  // forward: 8x8 blocks, two Gaussians per iteration (4 waves/tile)
 // backward geometry (gsplat_debug_set_raster_variant's bwd_pxl): 1 = 8x8 blocks, one pixel per
 // lane, two Gaussians per iteration (raster_bwd8_kernel); 2 = 16x8 strips, two pixels per lane
 // (raster_bwd3p_kernel); 0 = by frame size, see bwd_geometry()
 constexpr int BWD_PXL = 0;  // 0: by frame size (bwd_geometry)
 // Tuning / ablation knobs (gsplat_debug_set_raster_variant); defaults are the shipped ones.
-int g_fwd_pxl = FWD_PXL, g_bwd_pxl = BWD_PXL, g_bwd_flags = 0;
+int g_bwd_pxl = BWD_PXL, g_bwd_flags = 0;
 // forward staging pipelined one batch ahead (the PF instantiation, see RawG): -1 by frame
 // size (below 3,584 tiles, where the longest waves bound the launch), 0 off, 1 on
 // (gsplat_debug_set_raster_variant flags bits 28-29: 0 auto, 1 off, 2 on).  (The same pipeline
@@ -194,14 +193,12 @@ __device__ __forceinline__ float gs_vis(float sigma) {
 }
 
 __device__ __forceinline__ f2 vfma(f2 a, f2 b, f2 c) { return __builtin_elementwise_fma(a, b, c); }
-template <typename V>
-__device__ __forceinline__ V gs_sigma2v(float hc, float bdx, float hA, V dy) {
-  return vfma(vfma(V(hc), dy, V(bdx)), dy, V(hA));
+__device__ __forceinline__ f2 gs_sigma2v(float hc, float bdx, float hA, f2 dy) {
+  return vfma(vfma(f2(hc), dy, f2(bdx)), dy, f2(hA));
 }
-template <typename V>
-__device__ __forceinline__ V gs_vis2v(V sigma) {
-  const V e = sigma * NEG_LOG2E;
-  return V{__builtin_amdgcn_exp2f(e.x), __builtin_amdgcn_exp2f(e.y)};
+__device__ __forceinline__ f2 gs_vis2v(f2 sigma) {
+  const f2 e = sigma * NEG_LOG2E;
+  return f2{__builtin_amdgcn_exp2f(e.x), __builtin_amdgcn_exp2f(e.y)};
 }
 
 // Exactness-preserving cull of one Gaussian against the wave's pixel-centre rectangle
@@ -366,13 +363,10 @@ __device__ __forceinline__ RawG raw_load(int g, const float2 *__restrict__ xys,
   q.bl = colors[3 * g + 2];
   return q;
 }
-// stage_gaussian's cull and fill on prefetched data (BF: the branch-free cull of the backward)
-template <bool BF>
+// stage_gaussian<false>'s cull and fill on prefetched data
 __device__ __forceinline__ bool stage_raw(const RawG &q, bool live, int idx, int g, float rx0,
                                           float rx1, float ry0, float ry1, GStage &s) {
-  const bool keep =
-      live && (BF ? touches_rect_bf(q.xy.x, q.xy.y, q.a, q.b, q.c, q.o, rx0, rx1, ry0, ry1)
-                  : touches_rect(q.xy.x, q.xy.y, q.a, q.b, q.c, q.o, rx0, rx1, ry0, ry1));
+  const bool keep = live && touches_rect(q.xy.x, q.xy.y, q.a, q.b, q.c, q.o, rx0, rx1, ry0, ry1);
   if (keep) {
     s.x = q.xy.x;
     s.y = q.xy.y;
@@ -585,8 +579,24 @@ __device__ __forceinline__ void stage_kept(int idx, int g, const float2 *__restr
 
 // A workgroup of 4 waves covers 4 / (waves per tile) tiles.  A wave owns a COLS-wide
 // rectangle of its tile: lanes map to (column lane % COLS, row lane / COLS), and each lane
-// holds PXL pixels spaced 64 / COLS rows apart.  COLS = 16 gives full-width strips, COLS = 8
-// gives more compact blocks (fewer Gaussians touch an 8x8 block than a 16x4 strip).
+// holds PXL pixels spaced 64 / COLS rows apart.  The two footprints in use: the 8x8 block (one
+// pixel per lane, 4 waves per tile: the forward and raster_bwd8_kernel) and the 16x8 strip
+// (two pixels per lane 4 rows apart, 2 waves per tile: raster_bwd3p_kernel) -- fewer Gaussians
+// touch an 8x8 block than a 16x8 strip.
+struct Block8 {
+  static constexpr int COLS = 8, PXL = 1;
+};
+struct Strip {
+  static constexpr int COLS = 16, PXL = 2;
+};
+template <class G>
+constexpr int LANE_ROWS = 64 / G::COLS;  // rows between a lane's pixels
+template <class G>
+constexpr int WAVE_ROWS = LANE_ROWS<G> * G::PXL;
+template <class G>
+constexpr int WAVES_PER_TILE = (GS_BLOCK / G::COLS) * (GS_BLOCK / WAVE_ROWS<G>);
+template <class G>
+constexpr int TILES_PER_BLOCK = 4 / WAVES_PER_TILE<G>;
 struct WaveRect {
   bool live;
   int tile, j, i0;
@@ -688,28 +698,18 @@ __device__ __forceinline__ int block_slot() {
 }
 
 // Work slot of this wave: block slot * (tiles per workgroup) + wave / (waves per tile).
-template <int PXL, int COLS>
+template <class G>
 __device__ __forceinline__ int wave_slot() {
-  constexpr int WPT = (GS_BLOCK / COLS) * (GS_BLOCK / ((64 / COLS) * PXL));
-  return block_slot() * (4 / WPT) + (threadIdx.x >> 6) / WPT;
+  return block_slot() * TILES_PER_BLOCK<G> + (threadIdx.x >> 6) / WAVES_PER_TILE<G>;
 }
-template <int PXL, int COLS>
-__device__ __forceinline__ WaveRect wave_rect(int tbx, int tby, int H, int W, int tile = -1,
-                                              int wt_item = -1) {
-  constexpr int LROWS = 64 / COLS;      // rows per lane pass
-  constexpr int WROWS = LROWS * PXL;    // rows per wave
-  constexpr int WX = GS_BLOCK / COLS, WY = GS_BLOCK / WROWS;
-  constexpr int WPT = WX * WY;          // waves per tile
-  static_assert(WPT >= 1 && WPT <= 4 && 4 % WPT == 0, "wave footprint must tile 16x16");
+// The wave's rectangle of tile `tile` (-1: the wave's own work slot).
+template <class G>
+__device__ __forceinline__ WaveRect wave_rect(int tbx, int tby, int H, int W, int tile = -1) {
+  constexpr int COLS = G::COLS, WROWS = WAVE_ROWS<G>, WX = GS_BLOCK / COLS;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   WaveRect r;
-  if (tile >= 0) {
-    r.tile = tile;
-  } else {
-    const int slot = wave_slot<PXL, COLS>();
-    r.tile = slot;
-  }
-  const int wt = wt_item >= 0 ? wt_item : wave % WPT;
+  r.tile = tile >= 0 ? tile : wave_slot<G>();
+  const int wt = wave % WAVES_PER_TILE<G>;
   const int tx = r.tile % tbx, ty = r.tile / tbx;
   const int c0 = tx * GS_BLOCK + (wt % WX) * COLS, r0 = ty * GS_BLOCK + (wt / WX) * WROWS;
   r.live = r.tile < tbx * tby && c0 < W && r0 < H;
@@ -720,10 +720,6 @@ __device__ __forceinline__ WaveRect wave_rect(int tbx, int tby, int H, int W, in
   r.ry0 = (float)r0;
   r.ry1 = (float)min(r0 + WROWS - 1, H - 1);
   return r;
-}
-template <int PXL, int COLS>
-constexpr int tiles_per_block() {
-  return 4 / ((GS_BLOCK / COLS) * (GS_BLOCK / ((64 / COLS) * PXL)));
 }
 
 // ---- the fused L1 loss (gsplat_rasterize_forward_clearing_l1 / _backward_records_l1) ----
@@ -761,28 +757,26 @@ __device__ __forceinline__ void upstream_rgb(const L1Grad &l1, const float *__re
 }
 
 // ---------------------------------------------------------------- forward, C = 3
-// Two staged Gaussians per iteration (PXL pixels per lane, branch-free): both Gaussians'
-// sigma / exp / alpha are independent and evaluated together; only the transmittance
-// update is applied in list order, so every pixel sees exactly the scalar kernel's
-// sequence of operations.
+// 8x8 blocks, one pixel per lane, two staged Gaussians per iteration (branch-free): both
+// Gaussians' sigma / exp / alpha are independent and evaluated together; only the
+// transmittance update is applied in list order, so every pixel sees exactly the scalar
+// kernel's sequence of operations.
 //
 // DEPTH (fused RGB+depth eval render): each staged Gaussian also carries its
 // depth, accumulated with the same weight as the colour channels into out_depth -- exactly
 // channel 0 of a second render with colours = depth and a zero background (gc_model.py:
 // 225-238), without the second binning and traversal.
-template <int PXL, int COLS, bool DEPTH = false, bool CNT = false, bool PF = false>
+template <bool DEPTH = false, bool CNT = false, bool PF = false>
 __global__ __launch_bounds__(256) void raster_fwd3u_kernel(
     int tbx, int tby, int H, int W, const int *__restrict__ gids, const int2 *__restrict__ bins,
     const float2 *__restrict__ xys, const float *__restrict__ conics,
     const float *__restrict__ colors, const float *__restrict__ opacity,
     const float *__restrict__ background, float *__restrict__ out_img,
     float *__restrict__ final_Ts, int *__restrict__ final_idx,
-    const float *__restrict__ depths = nullptr, float *__restrict__ out_depth = nullptr,
-    float4 *__restrict__ zero = nullptr,
-    long long zero_n = 0, const int *__restrict__ zero_radii = nullptr,
-    int *__restrict__ tile_last = nullptr, unsigned long long *__restrict__ kbits = nullptr,
-    long long kbw = 0, const float *__restrict__ l1_gt = nullptr,
-    float *__restrict__ l1_part = nullptr, int l1_clamp = 0) {
+    const float *__restrict__ depths, float *__restrict__ out_depth, float4 *__restrict__ zero,
+    long long zero_n, const int *__restrict__ zero_radii, int *__restrict__ tile_last,
+    unsigned long long *__restrict__ kbits, long long kbw, const float *__restrict__ l1_gt,
+    float *__restrict__ l1_part, int l1_clamp) {
   // Side job: clear a buffer (the fused path's gradient records) with the memory bandwidth the
   // VALU-bound blend leaves idle -- a grid-stride sweep of coalesced 16-B stores, issued by each
   // wave as it finishes (issued first, the blend's first load wait would also wait for them:
@@ -794,10 +788,10 @@ __global__ __launch_bounds__(256) void raster_fwd3u_kernel(
         zero[k] = make_float4(0.f, 0.f, 0.f, 0.f);
   };
   const WaveLog wlog;
-  const WaveRect R = wave_rect<PXL, COLS>(tbx, tby, H, W);
+  const WaveRect R = wave_rect<Block8>(tbx, tby, H, W);
   // tile_last (the list-split plan's walk table, see split_work_kernel): per wave of a tile,
   // the largest final index of its pixels (-1: none in the image)
-  constexpr int WPT = (GS_BLOCK / COLS) * (GS_BLOCK / ((64 / COLS) * PXL));
+  constexpr int PXL = Block8::PXL, LROWS = LANE_ROWS<Block8>, WPT = WAVES_PER_TILE<Block8>;
   static_assert(WPT == SPLIT_WAVES, "one walk-table entry per wave of a tile");
   const int wt = (threadIdx.x >> 6) % WPT;
   // the fused L1 loss's per-wave partial l1_part[w] (gsplat_rasterize_forward_clearing_l1)
@@ -814,7 +808,6 @@ __global__ __launch_bounds__(256) void raster_fwd3u_kernel(
   const int tile = R.tile, j = R.j, i0 = R.i0;
   const float px = (float)j;
   const float rx0 = R.rx0, rx1 = R.rx1, ry0 = R.ry0, ry1 = R.ry1;
-  constexpr int LROWS = 64 / COLS;
   float py[PXL], T[PXL], cr[PXL], cg[PXL], cb[PXL], cd[PXL];
   int cur[PXL];
   bool done[PXL];
@@ -858,7 +851,7 @@ __global__ __launch_bounds__(256) void raster_fwd3u_kernel(
       pipe.g_next = pipe.g_after;
       pipe.r_next = raw_load(pipe.g_next, xys, conics, colors, opacity);
       pipe.g_after = gids[min(b + 128 + lane, range.y - 1)];
-      keep = stage_raw<false>(q, idx < range.y, idx, g, rx0, rx1, ry0, ry1, s);
+      keep = stage_raw(q, idx < range.y, idx, g, rx0, rx1, ry0, ry1, s);
     } else {
       keep = idx < range.y &&
              stage_gaussian(idx, gids, xys, conics, colors, opacity, rx0, rx1, ry0, ry1, s);
@@ -959,9 +952,10 @@ __global__ __launch_bounds__(256) void raster_fwd3u_kernel(
   clear_side_job();
 }
 
-// ---------------------------------------------------------------- backward, C = 3
-// Packed backward: 2*NP pixels per lane as float2 pairs, branch-free (an invalid pixel gets
-// alpha = vis = 0: T, the colour buffer and every partial sum are unchanged exactly).
+// ---------------------------------------------------------------- strip backward, C = 3
+// 16x8 strips: the lane's two pixels (4 rows apart) are one float2 pair, blended branch-free
+// (an invalid pixel gets alpha = vis = 0: T, the colour buffer and every partial sum are
+// unchanged exactly).
 // Per pixel the colour buffer enters v_alpha only through q - sum_c buf_c * v_c (q: the
 // background / alpha-output term below), carried as that one running value Qs (each Gaussian
 // behind subtracts fac * (colour . v_out) with one fma), and the
@@ -976,28 +970,31 @@ __global__ __launch_bounds__(256) void raster_fwd3u_kernel(
 // blend the part itself -- per pixel the same arithmetic in the same order as the unsplit
 // walk, so the per-wave totals (and the deterministic mode's sums) are unchanged, while a
 // long list's parts run as separate, earlier-dispatched waves.
-#define BWD3P_PARAMS                                                                         \
-    int tbx, int tby, int H, int W, const int *__restrict__ gids, const int2 *__restrict__ bins, \
-    const float2 *__restrict__ xys, const float *__restrict__ conics,                            \
-    const float *__restrict__ colors, const float *__restrict__ opacity,                         \
-    const float *__restrict__ background, const float *__restrict__ final_Ts,                    \
-    const int *__restrict__ final_idx, const float *__restrict__ v_out,                          \
-    const float *__restrict__ v_out_alpha, float alpha_max, float *__restrict__ rec, int chunk,  \
-    const int2 *__restrict__ items, const int *__restrict__ n_items,                             \
-    unsigned long long *__restrict__ det, const unsigned long long *__restrict__ kbits,          \
-    long long kbw, const int *__restrict__ tile_last, L1Grad l1
-#define BWD3P_ARGS                                                                           \
-  tbx, tby, H, W, gids, bins, xys, conics, colors, opacity, background, final_Ts, final_idx,  \
-      v_out, v_out_alpha, alpha_max, rec, chunk, items, n_items, det, kbits, kbw, tile_last, l1
-// One work item of the strip backward: tile `ctile` (-1: the wave's own slot), list part `part`
-// (SPLIT), strip `wt` of the tile (-1: by the wave's index in its workgroup).
-template <int NP, bool ATOMICS, int COLS, bool SPLIT, typename PV, bool DET, bool CNT, bool KB>
-__device__ __forceinline__ void bwd3p_item(BWD3P_PARAMS, int ctile, int part, int wt_item) {
-  constexpr int PXL = 2 * NP;
-  constexpr int LROWS = 64 / COLS;
+// KB: the kept positions come from the forward's keep bits (KeepSrc) instead of a cull of
+// every position.  DET: integer accumulation (det_add).  CNT: lane-slot accounting
+// (gsplat_debug_pair_count).
+template <bool SPLIT = false, bool DET = false, bool CNT = false, bool KB = false>
+__global__ __launch_bounds__(256) void raster_bwd3p_kernel(
+    int tbx, int tby, int H, int W, const int *__restrict__ gids, const int2 *__restrict__ bins,
+    const float2 *__restrict__ xys, const float *__restrict__ conics,
+    const float *__restrict__ colors, const float *__restrict__ opacity,
+    const float *__restrict__ background, const float *__restrict__ final_Ts,
+    const int *__restrict__ final_idx, const float *__restrict__ v_out,
+    const float *__restrict__ v_out_alpha, float alpha_max, float *__restrict__ rec, int chunk,
+    const int2 *__restrict__ items, const int *__restrict__ n_items,
+    unsigned long long *__restrict__ det, const unsigned long long *__restrict__ kbits,
+    long long kbw, const int *__restrict__ tile_last, L1Grad l1) {
+  int ctile = -1, part = 0;
+  if (SPLIT) {
+    const int slot = wave_slot<Strip>();
+    if (slot >= *n_items) return;  // wave-uniform: past the last item
+    const int2 it = items[slot];
+    ctile = it.x;
+    part = it.y;
+  }
   const WaveLog wlog;
   const unsigned long long at_t0 = GS_ATTR ? __builtin_amdgcn_s_memtime() : 0ull;
-  const WaveRect R = wave_rect<PXL, COLS>(tbx, tby, H, W, ctile, wt_item);
+  const WaveRect R = wave_rect<Strip>(tbx, tby, H, W, ctile);
   if (!R.live) return;  // wave-uniform
   __shared__ GStage lds[4][64];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -1005,12 +1002,12 @@ __device__ __forceinline__ void bwd3p_item(BWD3P_PARAMS, int ctile, int part, in
   const float px = (float)j;
   const float rx0 = R.rx0, rx1 = R.rx1, ry0 = R.ry0, ry1 = R.ry1;
   const float bg0 = background[0], bg1 = background[1], bg2 = background[2];
-  PV py[NP], T[NP], vr[NP], vg[NP], vb[NP], Qs[NP];
-  int binf[PXL];
+  f2 py, T, vr, vg, vb, Qs;  // .x: the pixel of row i0, .y: of row i0 + 4
+  int binf[2];
   int maxbin = -1;
 #pragma unroll
-  for (int k = 0; k < PXL; ++k) {
-    const int i = i0 + LROWS * k, p = k >> 1;
+  for (int k = 0; k < 2; ++k) {
+    const int i = i0 + LANE_ROWS<Strip> * k;
     float Tf = 0.f, r = 0.f, g = 0.f, bl = 0.f, a = 0.f;
     int bf = -1;
     if (i < H && j < W) {
@@ -1022,10 +1019,10 @@ __device__ __forceinline__ void bwd3p_item(BWD3P_PARAMS, int ctile, int part, in
     }
     // v_alpha's background/alpha terms: Tf/(1-alpha) * (v_alpha_out - bg . v_out)
     const float qk = Tf * (a - (bg0 * r + bg1 * g + bg2 * bl));
-    if (k & 1) {
-      py[p].y = (float)i; T[p].y = Tf; vr[p].y = r; vg[p].y = g; vb[p].y = bl; Qs[p].y = qk;
+    if (k) {
+      py.y = (float)i; T.y = Tf; vr.y = r; vg.y = g; vb.y = bl; Qs.y = qk;
     } else {
-      py[p].x = (float)i; T[p].x = Tf; vr[p].x = r; vg[p].x = g; vb[p].x = bl; Qs[p].x = qk;
+      py.x = (float)i; T.x = Tf; vr.x = r; vg.x = g; vb.x = bl; Qs.x = qk;
     }
     binf[k] = bf;
     maxbin = max(maxbin, bf);
@@ -1048,172 +1045,129 @@ __device__ __forceinline__ void bwd3p_item(BWD3P_PARAMS, int ctile, int part, in
   KeepSrc S{};
   if constexpr (KB) {
     // the strip's row half: blocks 2 wt, 2 wt + 1
-    const int wt = wt_item >= 0 ? wt_item : (threadIdx.x >> 6) & 1;
+    const int wt = (threadIdx.x >> 6) & 1;
     S = keep_src(kbits, kbw, tile_last, tile, range, 2 * wt, 2 * wt + 1);
   }
   auto stage1 = [&](int idx, int g, GStage &s) {
     stage_kept(idx, g, xys, conics, colors, opacity, s);
   };
+  // Stage and cull the positions top .. bottom (descending), 64 per round, and blend each round.
+  auto walk_culled = [&](int top, int bottom, auto &&blend) {
+    for (int b = top; b >= bottom; b -= 64) {
+      const int idx = b - lane;
+      GStage s;
+      const bool keep = idx >= bottom && stage_gaussian<true>(idx, gids, xys, conics, colors,
+                                                              opacity, rx0, rx1, ry0, ry1, s);
+      const unsigned long long kmask = __ballot(keep);
+      if (keep) stage[lanes_below(kmask)] = s;
+      const int n = __popcll(kmask);
+      wave_lds_sync();
+      blend(n);
+      wave_lds_sync();
+    }
+  };
   auto pre_blend = [&](int n) {
-    for (int t = 0; t < n; ++t) {
-        const GStage G = stage_at(stage, t);
-        const float dx = G.x - px;
-        const float hA = G.ha * dx * dx, bdx = G.b * dx;
-#pragma unroll
-        for (int p = 0; p < NP; ++p) {  // (the main loop's T / Qs operations, nothing else)
-          const PV dy = G.y - py[p];
-          const PV sig = gs_sigma2v<PV>(G.hc, bdx, hA, dy);
-          const PV vis = gs_vis2v<PV>(sig);
-          const PV ov = G.o * vis;
-          const PV al = {fminf(amax, ov.x), fminf(amax, ov.y)};
-          const bool v0 = G.idx <= binf[2 * p] && sig.x >= 0.f && al.x >= ALPHA_MIN;
-          const bool v1 = G.idx <= binf[2 * p + 1] && sig.y >= 0.f && al.y >= ALPHA_MIN;
-          const PV am = {v0 ? al.x : 0.f, v1 ? al.y : 0.f};
-          const PV om = 1.f - am;
-          const PV ra = {__builtin_amdgcn_rcpf(om.x), __builtin_amdgcn_rcpf(om.y)};
-          T[p] = T[p] * ra;
-          const PV fac = am * T[p];
-          const PV gv = vfma(PV(G.r), vr[p], vfma(PV(G.g), vg[p], G.bl * vb[p]));
-          Qs[p] = vfma(-fac, gv, Qs[p]);
-        }
+    for (int t = 0; t < n; ++t) {  // (the main loop's T / Qs operations, nothing else)
+      const GStage G = stage_at(stage, t);
+      const float dx = G.x - px;
+      const float hA = G.ha * dx * dx, bdx = G.b * dx;
+      const f2 dy = G.y - py;
+      const f2 sig = gs_sigma2v(G.hc, bdx, hA, dy);
+      const f2 vis = gs_vis2v(sig);
+      const f2 ov = G.o * vis;
+      const f2 al = {fminf(amax, ov.x), fminf(amax, ov.y)};
+      const bool v0 = G.idx <= binf[0] && sig.x >= 0.f && al.x >= ALPHA_MIN;
+      const bool v1 = G.idx <= binf[1] && sig.y >= 0.f && al.y >= ALPHA_MIN;
+      const f2 am = {v0 ? al.x : 0.f, v1 ? al.y : 0.f};
+      const f2 om = 1.f - am;
+      const f2 ra = {__builtin_amdgcn_rcpf(om.x), __builtin_amdgcn_rcpf(om.y)};
+      T = T * ra;
+      const f2 fac = am * T;
+      const f2 gv = vfma(f2(G.r), vr, vfma(f2(G.g), vg, G.bl * vb));
+      Qs = vfma(-fac, gv, Qs);
     }
   };
   if (SPLIT) {  // the positions behind this part: T and the colour behind only
-    if constexpr (KB) {
-      walk_kept(S, min(maxbin, range.y - 1), hi, stage, ahead, gids, stage1, pre_blend);
-    } else {
-      for (int b = min(maxbin, range.y - 1); b >= hi; b -= 64) {
-        const int idx = b - lane;
-        GStage s;
-        const bool keep = idx >= hi && stage_gaussian<true>(idx, gids, xys, conics, colors,
-                                                            opacity, rx0, rx1, ry0, ry1, s);
-        const unsigned long long kmask = __ballot(keep);
-        if (keep) stage[lanes_below(kmask)] = s;
-        const int n = __popcll(kmask);
-        wave_lds_sync();
-        pre_blend(n);
-        wave_lds_sync();
-      }
-    }
+    if constexpr (KB) walk_kept(S, min(maxbin, range.y - 1), hi, stage, ahead, gids, stage1, pre_blend);
+    else walk_culled(min(maxbin, range.y - 1), hi, pre_blend);
   }
   const int last = min(maxbin, hi - 1);
   unsigned c_slots = 0, c_live = 0, c_valid = 0;  // (CNT only)
   // (GS_ATTR: [0] blend, [1] tail, [2] prologue cycles, [3] rounds << 32 | iterations,
   //  [4] tail iterations, [5] life; cycles by s_memtime)
   unsigned long long at[6] = {0ull, 0ull, 0ull, 0ull, 0ull, 0ull};
+  // One staged Gaussian per iteration (two measured slower: register pressure).
   auto main_blend = [&](int n) {
-    constexpr int U = 1;  // (two per iteration measured slower: register pressure)
     unsigned long long at_b0 = 0;
     if constexpr (GS_ATTR) {
       at_b0 = __builtin_amdgcn_s_memtime();
       if (at[3] == 0) at[2] = at_b0 - at_t0;  // (the prologue: kernel start to first round)
       at[3] += (1ull << 32) + (unsigned long long)n;
     }
-    for (int t = 0; t < n; t += U) {
-      float rsum[U][7];  // sa, my, myy, r, g, b and dx: reduce_rec's inputs
-      bool anyv[U];
-      int gid[U];
-      unsigned long long anyw[U];
-      if constexpr (CNT) c_slots += U * PXL * 64;
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        GStage G = stage_at(stage, min(t + u, 63));
-        const bool live = t + u < n;
-        if (!live) G.r = G.g = G.bl = G.o = 0.f;  // stale slot: keep T / Qs finite
-        gid[u] = G.id;
-        // read with the rest of the staged record at the top of the iteration: left to the
-        // compiler, the id's LDS read sank to the atomic at the end -- a second LDS round trip
-        asm volatile("" : "+v"(gid[u]));
-        const float dx = G.x - px;
-        const float hA = G.ha * dx * dx, bdx = G.b * dx;
-        // per-lane sums as scalar dot products over the pixel pair (two scalar fmas cost what
-        // one packed fma does on gfx950, and need no packed horizontal add afterwards); the
-        // -o factor of the sigma gradient is applied once to the sums, not per pixel
-        float sr = 0.f, sg = 0.f, sb = 0.f, sa = 0.f, my = 0.f, myy = 0.f;
-        bool any = false;
-        unsigned long long anym = 0;  // wave mask of lanes with a valid pair (SGPR)
-#pragma unroll
-        for (int p = 0; p < NP; ++p) {
-          const PV dy = G.y - py[p];
-          const PV sig = gs_sigma2v<PV>(G.hc, bdx, hA, dy);
-          const PV vis = gs_vis2v<PV>(sig);
-          const PV ov = G.o * vis;
-          const PV al = {fminf(amax, ov.x), fminf(amax, ov.y)};
-          const bool v0 = live && G.idx <= binf[2 * p] && sig.x >= 0.f && al.x >= ALPHA_MIN;
-          const bool v1 =
-              live && G.idx <= binf[2 * p + 1] && sig.y >= 0.f && al.y >= ALPHA_MIN;
-          any = any || v0 || v1;
-          anym |= __builtin_amdgcn_ballot_w64(v0 || v1);
-          if constexpr (CNT) {
-            c_live += (live && G.idx <= binf[2 * p] ? 1u : 0u) +
-                      (live && G.idx <= binf[2 * p + 1] ? 1u : 0u);
-            c_valid += (v0 ? 1u : 0u) + (v1 ? 1u : 0u);
-          }
-          const PV am = {v0 ? al.x : 0.f, v1 ? al.y : 0.f};
-          const PV vm = {v0 ? vis.x : 0.f, v1 ? vis.y : 0.f};
-          const PV om = 1.f - am;
-          const PV ra = {__builtin_amdgcn_rcpf(om.x), __builtin_amdgcn_rcpf(om.y)};
-          T[p] = T[p] * ra;
-          const PV fac = am * T[p];
-          // (the first pair's terms start the sums: no 0 + x kept for signed zeros)
-          sr = fmaf(fac.y, vr[p].y, p ? fmaf(fac.x, vr[p].x, sr) : fac.x * vr[p].x);
-          sg = fmaf(fac.y, vg[p].y, p ? fmaf(fac.x, vg[p].x, sg) : fac.x * vg[p].x);
-          sb = fmaf(fac.y, vb[p].y, p ? fmaf(fac.x, vb[p].x, sb) : fac.x * vb[p].x);
-          const PV gv = vfma(
-              PV(G.r), vr[p], vfma(PV(G.g), vg[p], G.bl * vb[p]));
-          const PV v_alpha = vfma(gv, T[p], ra * Qs[p]);
-          Qs[p] = vfma(-fac, gv, Qs[p]);
-          const PV vva = vm * v_alpha;
-          const PV vdy = vva * dy;
-          sa = p ? sa + (vva.x + vva.y) : vva.x + vva.y;
-          my = fmaf(vva.y, dy.y, p ? fmaf(vva.x, dy.x, my) : vva.x * dy.x);
-          myy = fmaf(vdy.y, dy.y, p ? fmaf(vdy.x, dy.x, myy) : vdy.x * dy.x);
-        }
-        anyv[u] = any;
-        anyw[u] = anym;
-        // the record moments (common.h record_grads): the six lane sums and dx, which is
-        // constant along the lane's column -- reduce_rec forms sx, sxx, sxy from column sums
-        rsum[u][0] = sa; rsum[u][1] = my; rsum[u][2] = myy;
-        rsum[u][3] = sr; rsum[u][4] = sg; rsum[u][5] = sb; rsum[u][6] = dx;
+    for (int t = 0; t < n; ++t) {
+      if constexpr (CNT) c_slots += 2 * 64;
+      const GStage G = stage_at(stage, t);
+      int gid = G.id;
+      // read with the rest of the staged record at the top of the iteration: left to the
+      // compiler, the id's LDS read sank to the atomic at the end -- a second LDS round trip
+      asm volatile("" : "+v"(gid));
+      const float dx = G.x - px;
+      const float hA = G.ha * dx * dx, bdx = G.b * dx;
+      const f2 dy = G.y - py;
+      const f2 sig = gs_sigma2v(G.hc, bdx, hA, dy);
+      const f2 vis = gs_vis2v(sig);
+      const f2 ov = G.o * vis;
+      const f2 al = {fminf(amax, ov.x), fminf(amax, ov.y)};
+      const bool v0 = G.idx <= binf[0] && sig.x >= 0.f && al.x >= ALPHA_MIN;
+      const bool v1 = G.idx <= binf[1] && sig.y >= 0.f && al.y >= ALPHA_MIN;
+      const bool any = v0 || v1;
+      // wave mask of lanes with a valid pair (SGPR)
+      const unsigned long long anym = __builtin_amdgcn_ballot_w64(v0 || v1);
+      if constexpr (CNT) {
+        c_live += (G.idx <= binf[0] ? 1u : 0u) + (G.idx <= binf[1] ? 1u : 0u);
+        c_valid += (v0 ? 1u : 0u) + (v1 ? 1u : 0u);
       }
-      unsigned long long any_all = 0;
-#pragma unroll
-      for (int u = 0; u < U; ++u) any_all |= anyw[u];
-      if (any_all) {  // (an SGPR test, no VGPR round trip)
+      const f2 am = {v0 ? al.x : 0.f, v1 ? al.y : 0.f};
+      const f2 vm = {v0 ? vis.x : 0.f, v1 ? vis.y : 0.f};
+      const f2 om = 1.f - am;
+      const f2 ra = {__builtin_amdgcn_rcpf(om.x), __builtin_amdgcn_rcpf(om.y)};
+      T = T * ra;
+      const f2 fac = am * T;
+      // per-lane sums as scalar dot products over the pixel pair (two scalar fmas cost what
+      // one packed fma does on gfx950, and need no packed horizontal add afterwards); the
+      // -o factor of the sigma gradient is applied once to the sums, not per pixel
+      const float sr = fmaf(fac.y, vr.y, fac.x * vr.x);
+      const float sg = fmaf(fac.y, vg.y, fac.x * vg.x);
+      const float sb = fmaf(fac.y, vb.y, fac.x * vb.x);
+      const f2 gv = vfma(f2(G.r), vr, vfma(f2(G.g), vg, G.bl * vb));
+      const f2 v_alpha = vfma(gv, T, ra * Qs);
+      Qs = vfma(-fac, gv, Qs);
+      const f2 vva = vm * v_alpha;
+      const f2 vdy = vva * dy;
+      const float sa = vva.x + vva.y;
+      const float my = fmaf(vva.y, dy.y, vva.x * dy.x);
+      const float myy = fmaf(vdy.y, dy.y, vdy.x * dy.x);
+      if (anym) {  // (an SGPR test, no VGPR round trip)
         unsigned long long at_t = 0;
         if constexpr (GS_ATTR) at_t = __builtin_amdgcn_s_memtime();
-        float v[U];
+        // the record moments (common.h record_grads): the six lane sums and dx, which is
+        // constant along the lane's column -- reduce_rec forms sx, sxx, sxy from column sums
 #ifdef GS_ABLATE_NO_REDUCE  // attribution build (tools/attr_bwd.sh): a lane-local sum instead
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-          float s = rsum[u][0];
-#pragma unroll
-          for (int k = 1; k < 7; ++k) s += rsum[u][k];
-          v[u] = s;
-        }
+        const float v = sa + my + myy + sr + sg + sb + dx;
 #else
-#pragma unroll
-        for (int u = 0; u < U; ++u)
-          v[u] = reduce_rec(rsum[u][0], rsum[u][1], rsum[u][2], rsum[u][3], rsum[u][4],
-                            rsum[u][5], rsum[u][6]);
+        const float v = reduce_rec(sa, my, myy, sr, sg, sb, dx);
 #endif
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-          if constexpr (DET) {  // deterministic mode: exact integer sums of the wave totals
-            if (__any(anyv[u]) && slot >= 0)
-              det_add(det + ((size_t)gid[u] * REC_FIELDS + slot) * DET_LIMBS, v[u]);
-          } else if constexpr (ATOMICS) {
+        if constexpr (DET) {  // deterministic mode: exact integer sums of the wave totals
+          if (__any(any) && slot >= 0)
+            det_add(det + ((size_t)gid * REC_FIELDS + slot) * DET_LIMBS, v);
+        } else {
 #ifdef GS_ABLATE_NO_ATOMIC  // attribution build (tools/attr_bwd.sh): the total consumed, no add
-            asm volatile("" ::"v"(v[u]), "v"(gid[u]));
+          asm volatile("" ::"v"(v), "v"(gid));
 #else
-            // 32-bit element offset (the entry points reject N >= 2^27): the atomic takes the
-            // SGPR base + a VGPR offset, no 64-bit address arithmetic per iteration
-            if (anyw[u] && slot >= 0)
-              atomicAdd(rec + (uint32_t)(gid[u] * REC + slot), v[u]);
+          // 32-bit element offset (the entry points reject N >= 2^27): the atomic takes the
+          // SGPR base + a VGPR offset, no 64-bit address arithmetic per iteration
+          if (slot >= 0) atomicAdd(rec + (uint32_t)(gid * REC + slot), v);
 #endif
-          } else {
-            asm volatile("" ::"v"(v[u]));
-          }
         }
         if constexpr (GS_ATTR) {
           at[1] += __builtin_amdgcn_s_memtime() - at_t;
@@ -1223,42 +1177,14 @@ __device__ __forceinline__ void bwd3p_item(BWD3P_PARAMS, int ctile, int part, in
     }
     if constexpr (GS_ATTR) at[0] += __builtin_amdgcn_s_memtime() - at_b0;
   };
-  if constexpr (KB) {
-    walk_kept(S, last, lo, stage, ahead, gids, stage1, main_blend);
-  } else {
-    for (int b = last; b >= lo; b -= 64) {
-      const int idx = b - lane;
-      GStage s;
-      const bool keep = idx >= lo && stage_gaussian<true>(idx, gids, xys, conics, colors, opacity,
-                                                          rx0, rx1, ry0, ry1, s);
-      const unsigned long long kmask = __ballot(keep);
-      if (keep) stage[lanes_below(kmask)] = s;
-      const int n = __popcll(kmask);
-      wave_lds_sync();
-      main_blend(n);
-      wave_lds_sync();
-    }
-  }
+  if constexpr (KB) walk_kept(S, last, lo, stage, ahead, gids, stage1, main_blend);
+  else walk_culled(last, lo, main_blend);
   if constexpr (CNT) pair_count_flush(0, c_slots, c_live, c_valid);
   if constexpr (GS_ATTR) {
     at[5] = __builtin_amdgcn_s_memtime() - at_t0;
     if (at[3] == 0) at[2] = at[5];
   }
   wlog.done(tile, GS_ATTR ? at : nullptr);
-}
-
-template <int NP, bool ATOMICS, int COLS, bool SPLIT = false, typename PV = f2,
-          bool DET = false, bool CNT = false, bool KB = false>
-__global__ __launch_bounds__(256) void raster_bwd3p_kernel(BWD3P_PARAMS) {
-  int ctile = -1, part = 0;
-  if (SPLIT) {
-    const int slot = wave_slot<2 * NP, COLS>();
-    if (slot >= *n_items) return;  // wave-uniform: past the last item
-    const int2 it = items[slot];
-    ctile = it.x;
-    part = it.y;
-  }
-  bwd3p_item<NP, ATOMICS, COLS, SPLIT, PV, DET, CNT, KB>(BWD3P_ARGS, ctile, part, -1);
 }
 
 // ---------------------------------------------------------------- block backward (shipped)
@@ -1296,14 +1222,14 @@ __global__ __launch_bounds__(256) void raster_bwd8_kernel(
     const int *__restrict__ tile_last = nullptr, L1Grad l1 = {}) {
   int ctile = -1, part = 0;
   if (SPLIT) {
-    const int slot = wave_slot<1, 8>();
+    const int slot = wave_slot<Block8>();
     if (slot >= *n_items) return;  // wave-uniform: past the last item
     const int2 it = items[slot];
     ctile = it.x;
     part = it.y;
   }
   const WaveLog wlog;
-  const WaveRect R = wave_rect<1, 8>(tbx, tby, H, W, ctile);
+  const WaveRect R = wave_rect<Block8>(tbx, tby, H, W, ctile);
   if (!R.live) return;  // wave-uniform
   __shared__ GStage lds[4][64];
   const int wave = threadIdx.x >> 6;
@@ -1875,7 +1801,7 @@ static SplitWs carve_split_ws(void *base, long long T, long long I, int chunk) {
 }
 static bool default_variants() {
   // (the staging pipeline bits change the schedule only)
-  return g_fwd_pxl == FWD_PXL && g_bwd_pxl == BWD_PXL && (g_bwd_flags & ~(7 << 28)) == 0;
+  return g_bwd_pxl == BWD_PXL && (g_bwd_flags & ~(7 << 28)) == 0;
 }
 
 // Which list-split plans carry keep bits: the forward that fills a plan notes whether it also
@@ -1887,18 +1813,25 @@ static bool default_variants() {
 // the backward skips its split_plan_kernel.
 static std::mutex g_plan_kb_mu;
 static std::unordered_map<const void *, int> g_plan_kb;  // bit 0 keep bits, bit 1 plan ordered
-static void plan_kbits_note(const void *plan, bool written, bool planned = false) {
+// What a plan buffer holds when the backward gets it: the walk table, the keep bits, the
+// ordered items.
+struct PlanState {
+  bool work = false, kbits = false, ordered = false;
+};
+static void plan_note_set(const void *plan, PlanState s) {
   std::lock_guard<std::mutex> lk(g_plan_kb_mu);
   if (g_plan_kb.size() > 4096) g_plan_kb.clear();  // (stale entries of freed plans)
-  g_plan_kb[plan] = (written ? 1 : 0) | (planned ? 2 : 0);
+  g_plan_kb[plan] = (s.kbits ? 1 : 0) | (s.ordered ? 2 : 0);
 }
-static int plan_note(const void *plan) {
+// plan_filled (the caller's word that this frame's clearing forward filled the plan): the walk
+// table is there, the rest is what that forward noted.
+static PlanState plan_state(const void *plan, int plan_filled) {
+  if (!plan_filled) return PlanState{};
   std::lock_guard<std::mutex> lk(g_plan_kb_mu);
   const auto it = g_plan_kb.find(plan);
-  return it != g_plan_kb.end() ? it->second : 0;
+  const int note = it != g_plan_kb.end() ? it->second : 0;
+  return PlanState{true, (note & 1) != 0, (note & 2) != 0};
 }
-static bool plan_kbits_written(const void *plan) { return plan_note(plan) & 1; }
-static bool plan_ordered(const void *plan) { return plan_note(plan) & 2; }
 
 extern "C" int gsplat_rasterize_chunk_size(int tile_bounds_x, int tile_bounds_y,
                                            int64_t num_intersects) {
@@ -1936,31 +1869,95 @@ static bool bad_frame(int tbx, int tby, int H, int W) {
          (long long)tby * GS_BLOCK < H;
 }
 
-// The shipped C = 3 forward: 8x8 blocks, two Gaussians per iteration (CNT: the lane-slot
-// counting instantiation, same arithmetic), optional record clear.
+// ---- the C = 3 launch layer ----------------------------------------------------------------
+// The extern "C" entry points fill these bundles once; the kernels receive them expanded.
+// What every C = 3 blend launch shares: the frame, the sorted lists, the Gaussians.
+struct BlendArgs {
+  int tbx, tby, H, W;
+  const int32_t *gids, *bins;
+  const float *xys, *conics, *colors, *opacity, *background;
+  long long tiles() const { return (long long)tbx * tby; }
+  bool bad_frame() const { return ::bad_frame(tbx, tby, H, W); }
+};
+// The forward's outputs and optional jobs (null / 0: absent).
+struct FwdArgs {
+  float *out_img, *final_Ts;
+  int32_t *final_idx;
+  const float *depths = nullptr;  // DEPTH
+  float *out_depth = nullptr;
+  float4 *zero = nullptr;  // the side-job clear
+  long long zero_n = 0;
+  const int32_t *zero_radii = nullptr;
+  int *tile_last = nullptr;  // the list-split plan's walk table and keep bits
+  unsigned long long *kbits = nullptr;
+  long long kbw = 0;
+  const float *l1_gt = nullptr;  // the fused L1 loss
+  float *l1_part = nullptr;
+  int l1_clamp = 0;
+};
+// The backward's extras: the forward's state, the upstream gradients (v_output, or l1 when
+// l1.pred is set), the records it accumulates into.
+struct BwdArgs {
+  const float *final_Ts;
+  const int32_t *final_idx;
+  const float *v_output, *v_output_alpha;
+  L1Grad l1;
+  float alpha_max;
+  float *rec;
+  int n;
+};
+// A list-split plan buffer as the entry points receive it (chunk <= 0: no split).
+struct PlanBuf {
+  int64_t num_intersects;
+  int chunk;
+  void *buf;
+  size_t bytes;
+};
+// Carves p's workspace into w; false (error set) when the buffer is missing or too small.
+static bool carve_plan(const char *who, const BlendArgs &b, const PlanBuf &p, SplitWs &w) {
+  w = carve_split_ws(p.buf, b.tiles(), p.num_intersects, p.chunk);
+  if (p.buf && p.bytes >= w.bytes) return true;
+  set_error("%s: split plan buffer %zu < %zu bytes", who, p.bytes, w.bytes);
+  return false;
+}
+
+// Runtime bools to template arguments: with_flags(f, a, b, ...) calls
+// f(std::bool_constant<a>{}, std::bool_constant<b>{}, ...).
+template <bool... Bs, class F>
+static void with_flags(F &&f) {
+  f(std::bool_constant<Bs>{}...);
+}
+template <bool... Bs, class F, class... Rest>
+static void with_flags(F &&f, bool b, Rest... rest) {
+  if (b) with_flags<Bs..., true>(f, rest...);
+  else with_flags<Bs..., false>(f, rest...);
+}
+// The blend kernel variants that exist.  The launchers below never ask for another one, and
+// none is instantiated: the keep bits belong to a plan (KB needs SPLIT), the deterministic
+// mode wins over the pair count (never DET with CNT), and the depth render is not counted
+// (never CNT with DEPTH).
+constexpr bool bwd_variant(bool split, bool det, bool cnt, bool kb) {
+  return !(kb && !split) && !(det && cnt);
+}
+constexpr bool fwd_variant(bool depth, bool cnt) { return !(depth && cnt); }
+
+// The C = 3 forward: 8x8 blocks (CNT: the lane-slot counting instantiation, same arithmetic;
+// PF: staging pipelined one batch ahead), with f's optional jobs.
 template <bool DEPTH>
-static void launch_fwd(hipStream_t st, int tbx, int tby, int H, int W, const int32_t *gids,
-                       const int32_t *bins, const float *xys, const float *conics,
-                       const float *colors, const float *opacity, const float *background,
-                       float *out_img, float *final_Ts, int32_t *final_idx, const float *depths,
-                       float *out_depth, float4 *zero, long long zn, const int32_t *zero_radii,
-                       int *tile_last = nullptr, unsigned long long *kbits = nullptr,
-                       long long kbw = 0, const float *l1_gt = nullptr, float *l1_part = nullptr,
-                       int l1_clamp = 0) {
-  const unsigned grid = cdiv((long long)tbx * tby, (tiles_per_block<1, 8>()));
-#define FWDK(CNT, PF)                                                                      \
-  hipLaunchKernelGGL((raster_fwd3u_kernel<1, 8, DEPTH, CNT, PF>), dim3(grid), dim3(256), 0, st, \
-                     tbx, tby, H, W, gids, (const int2 *)bins, (const float2 *)xys, conics,     \
-                     colors, opacity, background, out_img, final_Ts, final_idx, depths,         \
-                     out_depth, zero, zn, zero_radii, tile_last, kbits, kbw, l1_gt, l1_part,    \
-                     l1_clamp)
-  const bool pf = pipelined_staging(tbx, tby);
-  if (!DEPTH && g_pair_count_on) {
-    if (pf) FWDK(true, true); else FWDK(true, false);
-  } else {
-    if (pf) FWDK(false, true); else FWDK(false, false);
-  }
-#undef FWDK
+static void launch_fwd(hipStream_t st, const BlendArgs &b, const FwdArgs &f) {
+  const unsigned grid = cdiv(b.tiles(), TILES_PER_BLOCK<Block8>);
+  with_flags(
+      [&](auto cnt, auto pf) {
+        constexpr bool CNT = decltype(cnt)::value, PF = decltype(pf)::value;
+        if constexpr (fwd_variant(DEPTH, CNT))
+          hipLaunchKernelGGL((raster_fwd3u_kernel<DEPTH, CNT, PF>), dim3(grid),
+                             dim3(256), 0, st, b.tbx, b.tby, b.H, b.W, b.gids,
+                             (const int2 *)b.bins, (const float2 *)b.xys, b.conics, b.colors,
+                             b.opacity, b.background, f.out_img, f.final_Ts, f.final_idx,
+                             f.depths, f.out_depth, f.zero, f.zero_n, f.zero_radii, f.tile_last,
+                             f.kbits, f.kbw, f.l1_gt, f.l1_part, f.l1_clamp);
+      },
+      !DEPTH && g_pair_count_on, pipelined_staging(b.tbx, b.tby));
 }
 
 extern "C" int gsplat_rasterize_forward(int tile_bounds_x, int tile_bounds_y, int img_height,
@@ -1980,9 +1977,9 @@ extern "C" int gsplat_rasterize_forward(int tile_bounds_x, int tile_bounds_y, in
   }
   const int T = tile_bounds_x * tile_bounds_y;
   if (channels == 3) {
-    launch_fwd<false>(st, tile_bounds_x, tile_bounds_y, img_height, img_width,
-                      gaussian_ids_sorted, tile_bins, xys, conics, colors, opacity, background,
-                      out_img, final_Ts, final_idx, nullptr, nullptr, nullptr, 0, nullptr);
+    const BlendArgs b{tile_bounds_x, tile_bounds_y, img_height, img_width, gaussian_ids_sorted,
+                      tile_bins, xys, conics, colors, opacity, background};
+    launch_fwd<false>(st, b, FwdArgs{out_img, final_Ts, final_idx});
   } else {
     ND_DISPATCH(raster_fwdn_kernel, tile_bounds_x, tile_bounds_y, img_height, img_width,
                 channels, gaussian_ids_sorted, (const int2 *)tile_bins, (const float2 *)xys,
@@ -2006,9 +2003,9 @@ extern "C" int gsplat_rasterize_forward_rgbd(int tile_bounds_x, int tile_bounds_
               tile_bounds_x, tile_bounds_y, img_height, img_width);
     return 1;
   }
-  launch_fwd<true>(st, tile_bounds_x, tile_bounds_y, img_height, img_width,
-                   gaussian_ids_sorted, tile_bins, xys, conics, colors, opacity, background,
-                   out_img, final_Ts, final_idx, depths, out_depth, nullptr, 0, nullptr);
+  const BlendArgs b{tile_bounds_x, tile_bounds_y, img_height, img_width, gaussian_ids_sorted,
+                    tile_bins, xys, conics, colors, opacity, background};
+  launch_fwd<true>(st, b, FwdArgs{out_img, final_Ts, final_idx, depths, out_depth});
   return check_launch("rasterize_forward_rgbd");
 }
 
@@ -2016,6 +2013,7 @@ extern "C" int gsplat_rasterize_forward_rgbd(int tile_bounds_x, int tile_bounds_
 // Measurement knob: bwd_pxl picks the backward geometry (BWD_PXL above); bits 20-27 of flags
 // the XCD chunk of the blend kernels' block order (0 the default K = 8, 255 dispatch order).
 extern "C" int gsplat_debug_set_raster_variant(int fwd_pxl, int bwd_pxl, int bwd_flags) {
+  // (fwd_pxl: the forward has one geometry, the 8x8 blocks)
   if (fwd_pxl != 1 || bwd_pxl < 0 || bwd_pxl > 2 || (bwd_flags & ~(0x7ff << 20)) ||
       ((bwd_flags >> 28) & 3) == 3) {
     set_error("debug_set_raster_variant: fwd_pxl must be 1, bwd_pxl 0 (by frame size), 1 (8x8 "
@@ -2024,7 +2022,6 @@ extern "C" int gsplat_debug_set_raster_variant(int fwd_pxl, int bwd_pxl, int bwd
               "30 (the forward's keep bits off)");
     return 1;
   }
-  g_fwd_pxl = fwd_pxl;
   g_bwd_pxl = bwd_pxl;
   g_bwd_flags = bwd_flags;
   g_keep_bits = !(bwd_flags & (1 << 30));
@@ -2079,123 +2076,104 @@ static int bwd_geometry(int tbx, int tby) {
   return (long long)tbx * tby < 3584 ? 1 : 2;
 }
 
-// The C = 3 backward into the records `rec` (which the caller cleared), with the list split
-// when w != NULL, the integer accumulators when det != NULL (then det_finish_kernel writes the
-// records), the lane-slot counting instantiation when the pair-count hook is on.
-static void launch_bwd(hipStream_t st, int tbx, int tby, int H, int W, int n,
-                       const int32_t *gids, const int32_t *bins, const float *xys,
-                       const float *conics, const float *colors, const float *opacity,
-                       const float *background, const float *final_Ts, const int32_t *final_idx,
-                       const float *v_output, const float *v_output_alpha, float alpha_max,
-                       float *rec, int chunk, const SplitWs *w, unsigned long long *det,
-                       bool work_ready = false, bool kbits_ready = false, L1Grad l1 = {},
-                       bool plan_ready = false) {
-  const long long slots = w ? w->items_bound : (long long)tbx * tby;
-  const int2 *its = w ? w->items : nullptr;
-  const int *ni = w ? w->n_items : nullptr;
-  if (w) {
-    const int T = tbx * tby;
-    if (!work_ready)  // (the forward did not fill the walk table)
-      hipLaunchKernelGGL(split_work_kernel, dim3(T), dim3(256), 0, st, tbx, tby, H, W, final_idx,
-                         w->work);
-    if (!(work_ready && plan_ready))  // (the forward's post_forward_kernel ordered it)
-      hipLaunchKernelGGL(split_plan_kernel, dim3(1), dim3(1024), 0, st, T, chunk,
-                         (const int2 *)bins, (const int *)w->work, w->items, w->n_items);
-  }
-  const bool cnt = g_pair_count_on && !det;
-  // the forward's keep bits: only when the forward that filled this plan also wrote them
-  // (plan_kbits_written: whatever g_keep_bits says now -- ADVICE r3)
-  const bool kb = w && work_ready && kbits_ready;
-  const unsigned long long *kbits = kb ? w->kbits : nullptr;
-  const long long kbw = kb ? w->kbw : 0;
-  const int *tl = kb ? w->work : nullptr;
-  if (bwd_geometry(tbx, tby) == 1) {
-    const unsigned grid = cdiv(slots, (tiles_per_block<1, 8>()));
-#define BWD8(CH, DET, CNT, KB)                                                             \
-  hipLaunchKernelGGL((raster_bwd8_kernel<CH, DET, CNT, KB>), dim3(grid), dim3(256), 0, st, tbx,  \
-                     tby, H, W, gids, (const int2 *)bins, (const float2 *)xys, conics, colors,  \
-                     opacity, background, final_Ts, final_idx, v_output, v_output_alpha,        \
-                     alpha_max, rec, chunk, its, ni, det, kbits, kbw, tl, l1)
-    if (w && kb) {
-      if (det) BWD8(true, true, false, true); else if (cnt) BWD8(true, false, true, true);
-      else BWD8(true, false, false, true);
-    } else if (w) {
-      if (det) BWD8(true, true, false, false); else if (cnt) BWD8(true, false, true, false);
-      else BWD8(true, false, false, false);
-    } else {
-      if (det) BWD8(false, true, false, false); else if (cnt) BWD8(false, false, true, false);
-      else BWD8(false, false, false, false);
-    }
-
-#undef BWD8
-  } else {
-    const unsigned grid = cdiv(slots, (tiles_per_block<2, 16>()));
-#define BWDS(CH, DET, CNT, KB)                                                             \
-  hipLaunchKernelGGL((raster_bwd3p_kernel<1, true, 16, CH, f2, DET, CNT, KB>), dim3(grid),       \
-                     dim3(256), 0, st, tbx, tby, H, W, gids, (const int2 *)bins,                \
-                     (const float2 *)xys, conics, colors, opacity, background, final_Ts,        \
-                     final_idx, v_output, v_output_alpha, alpha_max, rec, chunk, its, ni, det,  \
-                     kbits, kbw, tl, l1)
-    if (w && kb) {
-      if (det) BWDS(true, true, false, true); else if (cnt) BWDS(true, false, true, true);
-      else BWDS(true, false, false, true);
-    } else if (w) {
-      if (det) BWDS(true, true, false, false); else if (cnt) BWDS(true, false, true, false);
-      else BWDS(true, false, false, false);
-    } else {
-      if (det) BWDS(false, true, false, false); else if (cnt) BWDS(false, false, true, false);
-      else BWDS(false, false, false, false);
-    }
-#undef BWDS
-  }
-  if (det)
-    hipLaunchKernelGGL(det_finish_kernel, dim3(cdiv(n, 256)), dim3(256), 0, st, n, det, rec);
+// One backward blend kernel (K: raster_bwd8_kernel or raster_bwd3p_kernel of geometry G) over
+// `slots` work slots.
+template <class G, class Kernel>
+static void launch_bwd_kernel(Kernel kernel, hipStream_t st, long long slots, const BlendArgs &b,
+                              const BwdArgs &a, int chunk, const SplitWs *w,
+                              unsigned long long *det, bool kb) {
+  hipLaunchKernelGGL(kernel, dim3(cdiv(slots, TILES_PER_BLOCK<G>)), dim3(256), 0, st, b.tbx,
+                     b.tby, b.H, b.W, b.gids, (const int2 *)b.bins, (const float2 *)b.xys,
+                     b.conics, b.colors, b.opacity, b.background, a.final_Ts, a.final_idx,
+                     a.v_output, a.v_output_alpha, a.alpha_max, a.rec, chunk,
+                     w ? w->items : nullptr, w ? w->n_items : nullptr, det,
+                     kb ? w->kbits : nullptr, kb ? w->kbw : 0, kb ? w->work : nullptr, a.l1);
 }
 
-// Validates, leases the deterministic accumulators if on, and runs launch_bwd.
-static int backward_into_records(const char *who, hipStream_t st, int tbx, int tby, int H,
-                                 int W, int n, const int32_t *gids, const int32_t *bins,
-                                 const float *xys, const float *conics, const float *colors,
-                                 const float *opacity, const float *background,
-                                 const float *final_Ts, const int32_t *final_idx,
-                                 const float *v_output, const float *v_output_alpha,
-                                 float alpha_max, float *rec, int64_t num_intersects, int chunk,
-                                 void *plan, size_t plan_bytes, bool work_ready = false,
-                                 bool kbits_ready = false, L1Grad l1 = {},
-                                 bool plan_ready = false) {
-  SplitWs w{};
-  if (chunk > 0) {
-    w = carve_split_ws(plan, (long long)tbx * tby, num_intersects, chunk);
-    if (!plan || plan_bytes < w.bytes) {
-      set_error("%s: split plan buffer %zu < %zu bytes", who, plan_bytes, w.bytes);
-      return 1;
-    }
+// The C = 3 backward into the records a.rec (which the caller cleared), with the list split
+// when w != NULL, the integer accumulators when det != NULL (then det_finish_kernel writes the
+// records), the lane-slot counting instantiation when the pair-count hook is on.
+static void launch_bwd(hipStream_t st, const BlendArgs &b, const BwdArgs &a, int chunk,
+                       const SplitWs *w, unsigned long long *det, PlanState plan) {
+  const long long slots = w ? w->items_bound : b.tiles();
+  if (w) {
+    const int T = b.tbx * b.tby;
+    if (!plan.work)  // (the forward did not fill the walk table)
+      hipLaunchKernelGGL(split_work_kernel, dim3(T), dim3(256), 0, st, b.tbx, b.tby, b.H, b.W,
+                         a.final_idx, w->work);
+    if (!(plan.work && plan.ordered))  // (the forward's post_forward_kernel ordered it)
+      hipLaunchKernelGGL(split_plan_kernel, dim3(1), dim3(1024), 0, st, T, chunk,
+                         (const int2 *)b.bins, (const int *)w->work, w->items, w->n_items);
   }
+  // the forward's keep bits: only when the forward that filled this plan also wrote them
+  // (PlanState: whatever g_keep_bits says now -- ADVICE r3)
+  const bool kb = w && plan.work && plan.kbits;
+  const bool strips = bwd_geometry(b.tbx, b.tby) == 2;
+  with_flags(
+      [&](auto strip, auto split, auto det_on, auto cnt, auto keep) {
+        constexpr bool SPLIT = decltype(split)::value, DET = decltype(det_on)::value,
+                       CNT = decltype(cnt)::value, KB = decltype(keep)::value;
+        if constexpr (!bwd_variant(SPLIT, DET, CNT, KB)) return;
+        else if constexpr (decltype(strip)::value)
+          launch_bwd_kernel<Strip>(raster_bwd3p_kernel<SPLIT, DET, CNT, KB>, st, slots, b, a,
+                                   chunk, w, det, KB);
+        else
+          launch_bwd_kernel<Block8>(raster_bwd8_kernel<SPLIT, DET, CNT, KB>, st, slots, b, a,
+                                    chunk, w, det, KB);
+      },
+      strips, w != nullptr, det != nullptr, g_pair_count_on && !det, kb);
+  if (det)
+    hipLaunchKernelGGL(det_finish_kernel, dim3(cdiv(a.n, 256)), dim3(256), 0, st, a.n, det,
+                       a.rec);
+}
+
+// Carves the plan, leases the deterministic accumulators if on, and runs launch_bwd.
+static int backward_into_records(const char *who, hipStream_t st, const BlendArgs &b,
+                                 const BwdArgs &a, const PlanBuf &p, PlanState plan) {
+  SplitWs w{};
+  if (p.chunk > 0 && !carve_plan(who, b, p, w)) return 1;
+  const SplitWs *wp = p.chunk > 0 ? &w : nullptr;
   if (g_det) {
-    DetLease lease(n, st);
+    DetLease lease(a.n, st);
     if (!lease.buf) return check_launch(who);
-    launch_bwd(st, tbx, tby, H, W, n, gids, bins, xys, conics, colors, opacity, background,
-               final_Ts, final_idx, v_output, v_output_alpha, alpha_max, rec, chunk,
-               chunk > 0 ? &w : nullptr, lease.buf, work_ready, kbits_ready, l1, plan_ready);
+    launch_bwd(st, b, a, p.chunk, wp, lease.buf, plan);
     lease.finish();
   } else {
-    launch_bwd(st, tbx, tby, H, W, n, gids, bins, xys, conics, colors, opacity, background,
-               final_Ts, final_idx, v_output, v_output_alpha, alpha_max, rec, chunk,
-               chunk > 0 ? &w : nullptr, nullptr, work_ready, kbits_ready, l1, plan_ready);
+    launch_bwd(st, b, a, p.chunk, wp, nullptr, plan);
   }
   return 0;
 }
 
+struct GradOut {
+  float *v_xy, *v_conic, *v_colors, *v_opacity;
+};
 static void launch_split(hipStream_t st, int n, const float *rec, const float *conics,
-                         const float *opacity, float *v_xy, float *v_conic, float *v_colors,
-                         float *v_opacity) {
+                         const float *opacity, const GradOut &out) {
   hipLaunchKernelGGL(split_grads_kernel, dim3(cdiv(n, 256)), dim3(256), 0, st, n,
-                     (const float4 *)rec, conics, opacity, conic_y_full(), v_xy, v_conic,
-                     v_colors, v_opacity);
+                     (const float4 *)rec, conics, opacity, conic_y_full(), out.v_xy, out.v_conic,
+                     out.v_colors, out.v_opacity);
 }
 
 extern "C" size_t gsplat_rasterize_backward_workspace_size(int num_points, int channels) {
   return channels == 3 && num_points > 0 ? (size_t)num_points * REC * sizeof(float) : 0;
+}
+
+static bool bad_points(int n) { return n < 0 || n >= MAX_BWD_POINTS; }
+static bool bad_buffer(const void *buf, size_t bytes, size_t need) {
+  return bytes < need || (need && !buf);
+}
+
+// The C = 3 body of gsplat_rasterize_backward and _chunked (sizes validated): clears the records
+// in `workspace`, accumulates them (a.rec and a.n are set here) and writes gsplat's tensors.
+static int backward_c3(const char *who, hipStream_t st, const BlendArgs &b, BwdArgs a,
+                       const PlanBuf &p, void *workspace, const GradOut &out) {
+  if (a.n == 0) return check_launch(who);
+  a.rec = (float *)workspace;
+  note(hipMemsetAsync(a.rec, 0, gsplat_rasterize_backward_workspace_size(a.n, 3), st),
+       "hipMemsetAsync");
+  if (backward_into_records(who, st, b, a, p, PlanState{})) return 1;
+  launch_split(st, a.n, a.rec, b.conics, b.opacity, out);
+  return check_launch(who);
 }
 
 extern "C" int gsplat_rasterize_backward(int tile_bounds_x, int tile_bounds_y, int img_height,
@@ -2211,7 +2189,7 @@ extern "C" int gsplat_rasterize_backward(int tile_bounds_x, int tile_bounds_y, i
                                          size_t workspace_bytes, void *stream) {
   hipStream_t st = (hipStream_t)stream;
   if (bad_frame(tile_bounds_x, tile_bounds_y, img_height, img_width) || channels < 1 ||
-      channels > 64 || num_points < 0 || num_points >= MAX_BWD_POINTS) {
+      channels > 64 || bad_points(num_points)) {
     set_error("rasterize_backward: bad sizes (tiles=%dx%d H=%d W=%d C=%d N=%d)", tile_bounds_x,
               tile_bounds_y, img_height, img_width, channels, num_points);
     return 1;
@@ -2219,88 +2197,96 @@ extern "C" int gsplat_rasterize_backward(int tile_bounds_x, int tile_bounds_y, i
   const int T = tile_bounds_x * tile_bounds_y;
   if (channels == 3) {
     const size_t need = gsplat_rasterize_backward_workspace_size(num_points, channels);
-    if (workspace_bytes < need || (need && !workspace)) {
+    if (bad_buffer(workspace, workspace_bytes, need)) {
       set_error("rasterize_backward: workspace %zu < %zu bytes", workspace_bytes, need);
       return 1;
     }
-    if (num_points == 0) return check_launch("rasterize_backward");
-    float *rec = (float *)workspace;
-    note(hipMemsetAsync(rec, 0, need, st), "hipMemsetAsync");
-    if (backward_into_records("rasterize_backward", st, tile_bounds_x, tile_bounds_y,
-                              img_height, img_width, num_points, gaussian_ids_sorted, tile_bins,
-                              xys, conics, colors, opacity, background, final_Ts, final_idx,
-                              v_output, v_output_alpha, alpha_max, rec, 0, 0, nullptr, 0))
-      return 1;
-    launch_split(st, num_points, rec, conics, opacity, v_xy, v_conic, v_colors, v_opacity);
-  } else {
-    if (num_points > 0) {
-      note(hipMemsetAsync(v_xy, 0, (size_t)num_points * 2 * sizeof(float), st), "hipMemsetAsync");
-      note(hipMemsetAsync(v_conic, 0, (size_t)num_points * 3 * sizeof(float), st),
-           "hipMemsetAsync");
-      note(hipMemsetAsync(v_colors, 0, (size_t)num_points * channels * sizeof(float), st),
-           "hipMemsetAsync");
-      note(hipMemsetAsync(v_opacity, 0, (size_t)num_points * sizeof(float), st),
-           "hipMemsetAsync");
-    }
-    ND_DISPATCH(raster_bwdn_kernel, tile_bounds_x, tile_bounds_y, img_height, img_width,
-                channels, gaussian_ids_sorted, (const int2 *)tile_bins, (const float2 *)xys,
-                conics, colors, opacity, background, final_Ts, final_idx, v_output,
-                v_output_alpha, alpha_max, conic_y_full() ? 1.f : 0.5f, v_xy, v_conic, v_colors,
-                v_opacity);
+    const BlendArgs b{tile_bounds_x, tile_bounds_y, img_height, img_width, gaussian_ids_sorted,
+                      tile_bins, xys, conics, colors, opacity, background};
+    const BwdArgs a{final_Ts, final_idx, v_output, v_output_alpha, L1Grad{}, alpha_max, nullptr,
+                    num_points};
+    return backward_c3("rasterize_backward", st, b, a, PlanBuf{}, workspace,
+                       GradOut{v_xy, v_conic, v_colors, v_opacity});
   }
+  if (num_points > 0) {
+    note(hipMemsetAsync(v_xy, 0, (size_t)num_points * 2 * sizeof(float), st), "hipMemsetAsync");
+    note(hipMemsetAsync(v_conic, 0, (size_t)num_points * 3 * sizeof(float), st),
+         "hipMemsetAsync");
+    note(hipMemsetAsync(v_colors, 0, (size_t)num_points * channels * sizeof(float), st),
+         "hipMemsetAsync");
+    note(hipMemsetAsync(v_opacity, 0, (size_t)num_points * sizeof(float), st),
+         "hipMemsetAsync");
+  }
+  ND_DISPATCH(raster_bwdn_kernel, tile_bounds_x, tile_bounds_y, img_height, img_width,
+              channels, gaussian_ids_sorted, (const int2 *)tile_bins, (const float2 *)xys,
+              conics, colors, opacity, background, final_Ts, final_idx, v_output,
+              v_output_alpha, alpha_max, conic_y_full() ? 1.f : 0.5f, v_xy, v_conic, v_colors,
+              v_opacity);
   return check_launch("rasterize_backward");
 }
 
-static int forward_clearing_impl(
-    const char *who, int tile_bounds_x, int tile_bounds_y, int img_height, int img_width,
+extern "C" int gsplat_rasterize_backward_chunked(
+    int tile_bounds_x, int tile_bounds_y, int img_height, int img_width, int num_points,
     const int32_t *gaussian_ids_sorted, const int32_t *tile_bins, const float *xys,
     const float *conics, const float *colors, const float *opacity, const float *background,
-    float *out_img, float *final_Ts, int32_t *final_idx, void *clear, size_t clear_bytes,
-    const int32_t *clear_radii, int64_t num_intersects, int chunk, void *plan, size_t plan_bytes,
-    const float *l1_gt, float *l1_part, int l1_clamp, float *l1_loss, void *stream) {
-  if (bad_frame(tile_bounds_x, tile_bounds_y, img_height, img_width) || clear_bytes % 16 ||
-      (clear_bytes && !clear) || (clear_radii && clear_bytes % 64) || chunk < 0 ||
-      (chunk > 0 && (chunk % 64 || num_intersects < 0))) {
-    set_error("%s: bad sizes (tiles=%dx%d H=%d W=%d clear=%zu chunk=%d)", who, tile_bounds_x,
-              tile_bounds_y, img_height, img_width, clear_bytes, chunk);
+    const float *final_Ts, const int32_t *final_idx, const float *v_output,
+    const float *v_output_alpha, float alpha_max, float *v_xy, float *v_conic, float *v_colors,
+    float *v_opacity, int64_t num_intersects, int chunk, void *plan, size_t plan_bytes,
+    void *workspace, size_t workspace_bytes, void *stream) {
+  if (chunk <= 0)
+    return gsplat_rasterize_backward(tile_bounds_x, tile_bounds_y, img_height, img_width, 3,
+                                     num_points, gaussian_ids_sorted, tile_bins, xys, conics,
+                                     colors, opacity, background, final_Ts, final_idx, v_output,
+                                     v_output_alpha, alpha_max, v_xy, v_conic, v_colors,
+                                     v_opacity, workspace, workspace_bytes, stream);
+  const size_t need = gsplat_rasterize_backward_workspace_size(num_points, 3);
+  if (bad_frame(tile_bounds_x, tile_bounds_y, img_height, img_width) || bad_points(num_points) ||
+      chunk % 64 || num_intersects < 0 || bad_buffer(workspace, workspace_bytes, need)) {
+    set_error("rasterize_backward_chunked: bad sizes (tiles=%dx%d H=%d W=%d N=%d chunk=%d) or "
+              "workspace %zu < %zu bytes", tile_bounds_x, tile_bounds_y, img_height, img_width,
+              num_points, chunk, workspace_bytes, need);
     return 1;
   }
-  int *tile_last = nullptr;  // the list-split plan's walk table, filled by the blend's waves
-  unsigned long long *kbits = nullptr;  // and the backward's keep bits (KeepSrc)
-  long long kbw = 0;
-  if (chunk > 0) {
-    const SplitWs w =
-        carve_split_ws(plan, (long long)tile_bounds_x * tile_bounds_y, num_intersects, chunk);
-    if (!plan || plan_bytes < w.bytes) {
-      set_error("%s: split plan buffer %zu < %zu bytes", who, plan_bytes, w.bytes);
-      return 1;
-    }
-    tile_last = w.work;
-    if (g_keep_bits) {
-      kbits = w.kbits;
-      kbw = w.kbw;
-    }
-    plan_kbits_note(plan, kbits != nullptr, true);
+  const BlendArgs b{tile_bounds_x, tile_bounds_y, img_height, img_width, gaussian_ids_sorted,
+                    tile_bins, xys, conics, colors, opacity, background};
+  const BwdArgs a{final_Ts, final_idx, v_output, v_output_alpha, L1Grad{}, alpha_max, nullptr,
+                  num_points};
+  return backward_c3("rasterize_backward_chunked", (hipStream_t)stream, b, a,
+                     PlanBuf{num_intersects, chunk, plan, plan_bytes}, workspace,
+                     GradOut{v_xy, v_conic, v_colors, v_opacity});
+}
+
+// The clearing forward: f holds the outputs, the buffer to clear (f.zero, clear_bytes) and the
+// L1 job; the plan p's walk table, keep bits and item order are filled when p.chunk > 0.
+static int forward_clearing_impl(const char *who, hipStream_t st, const BlendArgs &b, FwdArgs f,
+                                 size_t clear_bytes, const PlanBuf &p, float *l1_loss) {
+  if (b.bad_frame() || clear_bytes % 16 || (clear_bytes && !f.zero) ||
+      (f.zero_radii && clear_bytes % 64) || p.chunk < 0 ||
+      (p.chunk > 0 && (p.chunk % 64 || p.num_intersects < 0))) {
+    set_error("%s: bad sizes (tiles=%dx%d H=%d W=%d clear=%zu chunk=%d)", who, b.tbx, b.tby, b.H,
+              b.W, clear_bytes, p.chunk);
+    return 1;
   }
-  launch_fwd<false>((hipStream_t)stream, tile_bounds_x, tile_bounds_y, img_height, img_width,
-                    gaussian_ids_sorted, tile_bins, xys, conics, colors, opacity, background,
-                    out_img, final_Ts, final_idx, nullptr, nullptr, (float4 *)clear,
-                    (long long)(clear_bytes / 16), clear_radii, tile_last, kbits, kbw, l1_gt,
-                    l1_part, l1_clamp);
+  f.zero_n = (long long)(clear_bytes / 16);
+  const bool plan_job = p.chunk > 0, loss_job = f.l1_part != nullptr;
+  SplitWs w{};
+  if (plan_job) {
+    if (!carve_plan(who, b, p, w)) return 1;
+    f.tile_last = w.work;  // the walk table, filled by the blend's waves
+    if (g_keep_bits) {     // and the backward's keep bits (KeepSrc)
+      f.kbits = w.kbits;
+      f.kbw = w.kbw;
+    }
+    plan_note_set(p.buf, PlanState{true, f.kbits != nullptr, true});
+  }
+  launch_fwd<false>(st, b, f);
   // the loss of the partials and the list-split plan, one launch (post_forward_kernel)
-  const bool plan_job = chunk > 0, loss_job = l1_part != nullptr;
   if (plan_job || loss_job) {
-    const long long T = (long long)tile_bounds_x * tile_bounds_y;
-    SplitWs w{};
-    if (plan_job) w = carve_split_ws(plan, T, num_intersects, chunk);
-    const int n_part = loss_job ? (int)(gsplat_rasterize_l1_partials_bytes(tile_bounds_x,
-                                                                          tile_bounds_y) / 4)
-                                : 0;
+    const int n_part = loss_job ? (int)(gsplat_rasterize_l1_partials_bytes(b.tbx, b.tby) / 4) : 0;
     hipLaunchKernelGGL(post_forward_kernel, dim3((plan_job ? 1 : 0) + (loss_job ? 1 : 0)),
-                       dim3(1024), 0, (hipStream_t)stream, n_part, l1_part,
-                       1.0 / (3.0 * img_height * img_width), l1_loss, (int)T, chunk,
-                       (const int2 *)tile_bins, (const int *)w.work, plan_job ? w.items : nullptr,
-                       w.n_items);
+                       dim3(1024), 0, st, n_part, f.l1_part, 1.0 / (3.0 * b.H * b.W), l1_loss,
+                       (int)b.tiles(), p.chunk, (const int2 *)b.bins, (const int *)w.work,
+                       w.items, w.n_items);
   }
   return check_launch(who);
 }
@@ -2314,17 +2300,20 @@ extern "C" int gsplat_rasterize_forward_clearing(
     float *out_img, float *final_Ts, int32_t *final_idx, void *clear, size_t clear_bytes,
     const int32_t *clear_radii, int64_t num_intersects, int chunk, void *plan, size_t plan_bytes,
     void *stream) {
-  return forward_clearing_impl("rasterize_forward_clearing", tile_bounds_x, tile_bounds_y,
-                               img_height, img_width, gaussian_ids_sorted, tile_bins, xys, conics,
-                               colors, opacity, background, out_img, final_Ts, final_idx, clear,
-                               clear_bytes, clear_radii, num_intersects, chunk, plan, plan_bytes,
-                               nullptr, nullptr, 0, nullptr, stream);
+  const BlendArgs b{tile_bounds_x, tile_bounds_y, img_height, img_width, gaussian_ids_sorted,
+                    tile_bins, xys, conics, colors, opacity, background};
+  FwdArgs f{out_img, final_Ts, final_idx};
+  f.zero = (float4 *)clear;
+  f.zero_radii = clear_radii;
+  return forward_clearing_impl("rasterize_forward_clearing", (hipStream_t)stream, b, f,
+                               clear_bytes, PlanBuf{num_intersects, chunk, plan, plan_bytes},
+                               nullptr);
 }
 
 // The per-wave L1 partials of gsplat_rasterize_forward_clearing_l1 (one float per wave).
 extern "C" size_t gsplat_rasterize_l1_partials_bytes(int tile_bounds_x, int tile_bounds_y) {
   if (tile_bounds_x <= 0 || tile_bounds_y <= 0) return 0;
-  const long long grid = cdiv((long long)tile_bounds_x * tile_bounds_y, (tiles_per_block<1, 8>()));
+  const long long grid = cdiv((long long)tile_bounds_x * tile_bounds_y, TILES_PER_BLOCK<Block8>);
   return (size_t)grid * 4 * sizeof(float);
 }
 
@@ -2343,50 +2332,16 @@ extern "C" int gsplat_rasterize_forward_clearing_l1(
               need);
     return 1;
   }
-  if (forward_clearing_impl(who, tile_bounds_x, tile_bounds_y, img_height, img_width,
-                            gaussian_ids_sorted, tile_bins, xys, conics, colors, opacity,
-                            background, out_img, final_Ts, final_idx, clear, clear_bytes,
-                            clear_radii, num_intersects, chunk, plan, plan_bytes, gt, partials,
-                            clamp_pred ? 1 : 0, loss, stream))
-    return 1;
-  return check_launch(who);
-}
-
-extern "C" int gsplat_rasterize_backward_chunked(
-    int tile_bounds_x, int tile_bounds_y, int img_height, int img_width, int num_points,
-    const int32_t *gaussian_ids_sorted, const int32_t *tile_bins, const float *xys,
-    const float *conics, const float *colors, const float *opacity, const float *background,
-    const float *final_Ts, const int32_t *final_idx, const float *v_output,
-    const float *v_output_alpha, float alpha_max, float *v_xy, float *v_conic, float *v_colors,
-    float *v_opacity, int64_t num_intersects, int chunk, void *plan, size_t plan_bytes,
-    void *workspace, size_t workspace_bytes, void *stream) {
-  if (chunk <= 0)
-    return gsplat_rasterize_backward(tile_bounds_x, tile_bounds_y, img_height, img_width, 3,
-                                     num_points, gaussian_ids_sorted, tile_bins, xys, conics,
-                                     colors, opacity, background, final_Ts, final_idx, v_output,
-                                     v_output_alpha, alpha_max, v_xy, v_conic, v_colors,
-                                     v_opacity, workspace, workspace_bytes, stream);
-  hipStream_t st = (hipStream_t)stream;
-  const size_t need = gsplat_rasterize_backward_workspace_size(num_points, 3);
-  if (bad_frame(tile_bounds_x, tile_bounds_y, img_height, img_width) || num_points < 0 ||
-      num_points >= MAX_BWD_POINTS || chunk % 64 || num_intersects < 0 ||
-      workspace_bytes < need || (need && !workspace)) {
-    set_error("rasterize_backward_chunked: bad sizes (tiles=%dx%d H=%d W=%d N=%d chunk=%d) or "
-              "workspace %zu < %zu bytes", tile_bounds_x, tile_bounds_y, img_height, img_width,
-              num_points, chunk, workspace_bytes, need);
-    return 1;
-  }
-  if (num_points == 0) return check_launch("rasterize_backward_chunked");
-  float *rec = (float *)workspace;
-  note(hipMemsetAsync(rec, 0, need, st), "hipMemsetAsync");
-  if (backward_into_records("rasterize_backward_chunked", st, tile_bounds_x, tile_bounds_y,
-                            img_height, img_width, num_points, gaussian_ids_sorted, tile_bins, xys,
-                            conics, colors, opacity, background, final_Ts, final_idx, v_output,
-                            v_output_alpha, alpha_max, rec, num_intersects, chunk, plan,
-                            plan_bytes))
-    return 1;
-  launch_split(st, num_points, rec, conics, opacity, v_xy, v_conic, v_colors, v_opacity);
-  return check_launch("rasterize_backward_chunked");
+  const BlendArgs b{tile_bounds_x, tile_bounds_y, img_height, img_width, gaussian_ids_sorted,
+                    tile_bins, xys, conics, colors, opacity, background};
+  FwdArgs f{out_img, final_Ts, final_idx};
+  f.zero = (float4 *)clear;
+  f.zero_radii = clear_radii;
+  f.l1_gt = gt;
+  f.l1_part = partials;
+  f.l1_clamp = clamp_pred ? 1 : 0;
+  return forward_clearing_impl(who, (hipStream_t)stream, b, f, clear_bytes,
+                               PlanBuf{num_intersects, chunk, plan, plan_bytes}, loss);
 }
 
 extern "C" int gsplat_grad_records_split(int num_points, const void *records,
@@ -2401,8 +2356,8 @@ extern "C" int gsplat_grad_records_split(int num_points, const void *records,
     return 1;
   }
   if (num_points == 0) return 0;
-  launch_split((hipStream_t)stream, num_points, (const float *)records, conics, opacity, v_xy,
-               v_conic, v_colors, v_opacity);
+  launch_split((hipStream_t)stream, num_points, (const float *)records, conics, opacity,
+               GradOut{v_xy, v_conic, v_colors, v_opacity});
   return check_launch("grad_records_split");
 }
 
@@ -2410,32 +2365,23 @@ extern "C" size_t gsplat_grad_records_bytes(int num_points) {
   return num_points > 0 ? (size_t)num_points * REC * sizeof(float) : 0;
 }
 
-static int backward_records_impl(
-    const char *who, int tile_bounds_x, int tile_bounds_y, int img_height, int img_width,
-    int num_points, const int32_t *gaussian_ids_sorted, const int32_t *tile_bins, const float *xys,
-    const float *conics, const float *colors, const float *opacity, const float *background,
-    const float *final_Ts, const int32_t *final_idx, const float *v_output,
-    const float *v_output_alpha, float alpha_max, int64_t num_intersects, int chunk,
-    void *plan, size_t plan_bytes, int plan_filled, void *records, size_t records_bytes,
-    L1Grad l1, void *stream) {
-  hipStream_t st = (hipStream_t)stream;
-  const size_t need = gsplat_grad_records_bytes(num_points);
-  if (bad_frame(tile_bounds_x, tile_bounds_y, img_height, img_width) || num_points < 0 ||
-      num_points >= MAX_BWD_POINTS || num_intersects < 0 || (chunk > 0 && chunk % 64) ||
-      records_bytes < need || (need && !records) || (!v_output && !l1.pred)) {
+// The record backward of the fused path (a.rec: the records the forward cleared).  plan_filled:
+// the plan in p was filled by this frame's clearing forward, whose note says what it holds.
+static int backward_records_impl(const char *who, hipStream_t st, const BlendArgs &b,
+                                 const BwdArgs &a, const PlanBuf &p, int plan_filled,
+                                 size_t records_bytes) {
+  const size_t need = gsplat_grad_records_bytes(a.n);
+  if (b.bad_frame() || bad_points(a.n) || p.num_intersects < 0 ||
+      (p.chunk > 0 && p.chunk % 64) || bad_buffer(a.rec, records_bytes, need) ||
+      (!a.v_output && !a.l1.pred)) {
     set_error("%s: bad sizes (tiles=%dx%d H=%d W=%d N=%d chunk=%d records %zu < %zu bytes) or "
-              "no upstream gradient", who, tile_bounds_x, tile_bounds_y, img_height, img_width,
-              num_points, chunk, records_bytes, need);
+              "no upstream gradient", who, b.tbx, b.tby, b.H, b.W, a.n, p.chunk, records_bytes,
+              need);
     return 1;
   }
-  if (num_points == 0 || num_intersects == 0) return check_launch(who);
+  if (a.n == 0 || p.num_intersects == 0) return check_launch(who);
   // deterministic mode: the records' clear by the forward is superseded by det_finish_kernel
-  if (backward_into_records(who, st, tile_bounds_x, tile_bounds_y, img_height, img_width,
-                            num_points, gaussian_ids_sorted, tile_bins, xys, conics, colors,
-                            opacity, background, final_Ts, final_idx, v_output, v_output_alpha,
-                            alpha_max, (float *)records, num_intersects, chunk, plan, plan_bytes,
-                            plan_filled != 0, plan_filled != 0 && plan_kbits_written(plan), l1,
-                            plan_filled != 0 && plan_ordered(plan)))
+  if (backward_into_records(who, st, b, a, p, plan_state(p.buf, plan_filled)))
     return 1;
   return check_launch(who);
 }
@@ -2448,11 +2394,13 @@ extern "C" int gsplat_rasterize_backward_records(
     const float *v_output_alpha, float alpha_max, int64_t num_intersects, int chunk,
     void *plan, size_t plan_bytes, int plan_filled, void *records, size_t records_bytes,
     void *stream) {
-  return backward_records_impl("rasterize_backward_records", tile_bounds_x, tile_bounds_y,
-                               img_height, img_width, num_points, gaussian_ids_sorted, tile_bins,
-                               xys, conics, colors, opacity, background, final_Ts, final_idx,
-                               v_output, v_output_alpha, alpha_max, num_intersects, chunk, plan,
-                               plan_bytes, plan_filled, records, records_bytes, L1Grad{}, stream);
+  const BlendArgs b{tile_bounds_x, tile_bounds_y, img_height, img_width, gaussian_ids_sorted,
+                    tile_bins, xys, conics, colors, opacity, background};
+  const BwdArgs a{final_Ts, final_idx, v_output, v_output_alpha, L1Grad{}, alpha_max,
+                  (float *)records, num_points};
+  return backward_records_impl("rasterize_backward_records", (hipStream_t)stream, b, a,
+                               PlanBuf{num_intersects, chunk, plan, plan_bytes}, plan_filled,
+                               records_bytes);
 }
 
 extern "C" int gsplat_rasterize_backward_records_l1(
@@ -2469,9 +2417,11 @@ extern "C" int gsplat_rasterize_backward_records_l1(
   }
   const L1Grad l1{pred, gt, grad_loss, (float)(1.0 / (3.0 * img_height * img_width)),
                   clamp_pred ? 1 : 0};
-  return backward_records_impl("rasterize_backward_records_l1", tile_bounds_x, tile_bounds_y,
-                               img_height, img_width, num_points, gaussian_ids_sorted, tile_bins,
-                               xys, conics, colors, opacity, background, final_Ts, final_idx,
-                               nullptr, nullptr, alpha_max, num_intersects, chunk, plan,
-                               plan_bytes, plan_filled, records, records_bytes, l1, stream);
+  const BlendArgs b{tile_bounds_x, tile_bounds_y, img_height, img_width, gaussian_ids_sorted,
+                    tile_bins, xys, conics, colors, opacity, background};
+  const BwdArgs a{final_Ts, final_idx, nullptr, nullptr, l1, alpha_max, (float *)records,
+                  num_points};
+  return backward_records_impl("rasterize_backward_records_l1", (hipStream_t)stream, b, a,
+                               PlanBuf{num_intersects, chunk, plan, plan_bytes}, plan_filled,
+                               records_bytes);
 }

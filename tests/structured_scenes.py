@@ -433,6 +433,40 @@ def clamped(seed=6):
     return Structured("clamped", sc, cam, pre, info, st)
 
 
+@functools.lru_cache(maxsize=None)
+def dispatch_cells(seed=7):
+    """The tiny scene of the backward's dispatch cells ({8x8, strips} x {unsplit, split, split +
+    keep bits} x {atomic, deterministic, pair count}): a 40x48 frame (3x3 tiles, the right column
+    8 pixels wide), 260 low-opacity Gaussians inside the centre tile that every pixel of it walks
+    to the end (a forced chunk of 64 cuts the walk into five parts) and 120 of opacity 0.3 over
+    the whole frame, in front of and behind them."""
+    cam = synthetic_camera(40, 48)
+    rng = np.random.default_rng(seed)
+    n_deep, n_rest = 260, 120
+    px, py = _lattice(rng, n_deep, 20.5, 26.5, 20.5, 26.5)
+    qx, qy = _lattice(rng, n_rest, 1.0, 38.0, 1.0, 46.0)
+    z = np.r_[rng.uniform(-0.1, 0.1, n_deep), rng.uniform(0.15, 0.3, n_rest // 2),
+              rng.uniform(-0.3, -0.15, n_rest - n_rest // 2)]
+    n = n_deep + n_rest
+    rgb = rng.uniform(0.1, 0.9, (n, 3))
+    opacity = np.r_[np.full(n_deep, DEEP_OPACITY), np.full(n_rest, 0.3)]
+    sc = make_scene(cam, np.r_[px, qx], np.r_[py, qy], z, np.full(n, SCALE), opacity, rgb)
+    st = oracle_state(sc, cam)
+    f = st["fwd"]
+    lo, hi = (int(v) for v in st["bins"][CENTRE])
+    walk = int(f["final_idx"][16:32, 16:32].max()) - lo + 1
+    lens = st["bins"][:, 1] - st["bins"][:, 0]
+    info = dict(list_len=hi - lo, walk=walk, list_lens=[int(v) for v in lens],
+                final_T_min=float(f["final_Ts"].min()), num_intersects=int(f["num_intersects"]))
+    pre = {"3x3 tiles, the right column partial": tuple(cam.tile_bounds[:2]) == (3, 3) and
+           cam.width % 16 != 0,
+           "centre tile list > 192": hi - lo > 192,
+           "centre tile walk > 192 (>= 4 parts of 64)": walk > 192,
+           "every tile has a list": bool((lens > 0).all()),
+           "no pixel terminates": info["final_T_min"] > 1e-3}
+    return Structured("dispatch_cells", sc, cam, pre, info, st)
+
+
 def oracle_state_xys(scene, cam):
     scales = torch.exp(scene.scales).numpy()
     return O.project_forward(scene.means.numpy(), scales, 1.0, scene.quats.numpy(),
@@ -453,5 +487,6 @@ def all_scenes():
     out += [("sparse_windows", sparse_windows), ("early_exit", early_exit),
             ("depth_ties", depth_ties)]
     out += [(f"tiny_frame-{W}x{H}", functools.partial(tiny_frame, W, H)) for W, H in TINY_SIZES]
-    out += [("below_threshold", below_threshold), ("clamped", clamped)]
+    out += [("below_threshold", below_threshold), ("clamped", clamped),
+            ("dispatch_cells", dispatch_cells)]
     return out

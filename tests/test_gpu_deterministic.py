@@ -206,3 +206,35 @@ def test_keep_bits_switch_between_forward_and_backward(gpu, deterministic, hooks
         _lib.call("gsplat_debug_set_raster_variant", 1, 0, 0)
     for name, x, y in zip(("means", "scales", "quats", "opacities", "dc", "rest"), got, ref):
         np.testing.assert_array_equal(x, y, err_msg=name)
+
+
+@pytest.mark.parametrize("bwd", [1, 2], ids=["blocks8x8", "strips16x8"])
+def test_list_modes_bit_identical_records(gpu, deterministic, bwd, hooks, oracle_lib):
+    """The three list modes of one geometry -- the unsplit walk, the list split (chunk 64: five
+    parts of the centre tile) and the list split on the forward's keep bits -- add the same
+    per-wave totals, so the deterministic records (the four raster-level gradients) are equal bit
+    for bit, on the tiny 40x48 scene of tests/structured_scenes.py (dispatch_cells)."""
+    import structured_scenes as S
+    s = S.dispatch_cells()
+    bg = torch.from_numpy(s.state["bg"]).to(gpu)
+    gen = torch.Generator().manual_seed(77)
+    v_img = torch.randn(s.H, s.W, 3, generator=gen).to(gpu)
+    v_alpha = torch.randn(s.H, s.W, generator=gen).to(gpu)
+    got = {}
+    try:
+        for lists, (chunk, flags) in (("unsplit", (-1, 0)), ("split", (64, 1 << 30)),
+                                      ("split-keep", (64, 0))):
+            _lib.call("gsplat_debug_set_chunk", chunk)
+            _lib.call("gsplat_debug_set_raster_variant", 1, bwd, flags)
+            out = render_fused(s.scene.to(gpu).requires_grad_(), s.cam.to(gpu), 0, bg,
+                               return_alpha=True, clamp=False)
+            ((out["rgb"] * v_img).sum() + (out["accumulation"][..., 0] * v_alpha).sum()).backward()
+            got[lists] = [g.detach().cpu().numpy() for g in out["raster_grads"]()]
+    finally:
+        _lib.call("gsplat_debug_set_chunk", 0)
+        _lib.call("gsplat_debug_set_raster_variant", 1, 0, 0)
+    for lists in ("split", "split-keep"):
+        for name, x, y in zip(("v_xy", "v_conic", "v_colors", "v_opacity"), got["unsplit"],
+                              got[lists]):
+            assert np.abs(x).max() > 0, name
+            np.testing.assert_array_equal(y, x, err_msg=f"{lists} {name}")

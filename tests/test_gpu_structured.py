@@ -246,6 +246,35 @@ def test_backward_alternative(gpu, scene, hooks):
         _lib.set_deterministic(prev)
 
 
+# ---- every cell of the backward's kernel dispatch ---------------------------------------------
+
+# list mode -> (gsplat_debug_set_chunk, raster-variant flags): the keep bits exist only behind
+# render_fused's plan-filling forward (the gsplat API caller's split walks without them)
+LIST_MODES = {"unsplit": (-1, 0), "split": (64, 1 << 30), "split-keep": (64, 0)}
+
+
+@pytest.mark.parametrize("det", [False, True], ids=["atomic", "deterministic"])
+@pytest.mark.parametrize("lists", list(LIST_MODES))
+@pytest.mark.parametrize("bwd", [1, 2], ids=["blocks8x8", "strips16x8"])
+@pytest.mark.parametrize("scene", ["dispatch_cells"], indirect=True)
+def test_backward_dispatch_cells(gpu, scene, bwd, lists, det, hooks):
+    """{8x8 blocks, 16x8 strips} x {unsplit, split, split + keep bits} x {atomic, deterministic}
+    on the tiny 40x48 scene (a forced chunk of 64: five parts of the centre tile): forward and
+    the four raster-level gradients of both callers vs the oracle.  (The pair-count
+    instantiations of the same cells: tests/test_gpu_pair_count.py; bit-identity of the
+    deterministic records across the list modes: tests/test_gpu_deterministic.py.)"""
+    chunk, flags = LIST_MODES[lists]
+    prev = _lib.set_deterministic(det)
+    try:
+        _lib.call("gsplat_debug_set_chunk", chunk)
+        _lib.call("gsplat_debug_set_raster_variant", 1, bwd, flags)
+        _check_both_callers(gpu, scene, f"{scene.name} bwd{bwd} {lists}")
+    finally:
+        _lib.call("gsplat_debug_set_chunk", 0)
+        _lib.call("gsplat_debug_set_raster_variant", 1, 0, 0)
+        _lib.set_deterministic(prev)
+
+
 # ---- the shipped split plan, unforced -----------------------------------------------------------
 
 @pytest.mark.parametrize("scene", SPLIT, indirect=True)
