@@ -11,7 +11,8 @@ Layout:
   formats.py            transforms.json / sparse_pc.ply / splatfacto ckpt loaders
   train.py              multi-view data-parallel train step (fused loss, fused Adam)
   exchange.py           data-parallel SH-gradient view exchange (RCCL all-gather)
-  loss.py  optim.py     fused L1+SSIM loss, fused multi-tensor Adam
+  loss.py  optim.py     fused L1+SSIM loss, fused multi-tensor Adam (optionally row-frozen)
+  lift.py               splat-back: 2D masks lifted onto the Gaussians, labels rendered back
   quirks.py             the gsplat 0.1.2.1 [VERIFY] behaviour switch (GSPLAT_MI355X_QUIRKS)
   set_deterministic     bit-reproducible rasterize backward (GSPLAT_MI355X_DETERMINISTIC=1)
 
@@ -19,6 +20,7 @@ Layout:
 """
 from . import quirks
 from ._lib import set_deterministic
+from .lift import LiftResult, lift_masks, lift_sums, render_labels, select, splat_back
 from .project_gaussians import project_gaussians
 from .rasterize import rasterize_gaussians, rasterize_gaussians_rgbd
 from .sh import num_sh_bases, spherical_harmonics
@@ -41,4 +43,10 @@ __all__ = [
     "get_tile_bin_edges",
     "quirks",
     "set_deterministic",
+    "splat_back",
+    "lift_masks",
+    "lift_sums",
+    "select",
+    "render_labels",
+    "LiftResult",
 ]

@@ -120,6 +120,9 @@ SIGNATURES = {
     "gsplat_density_accumulate": (_I, [_I, _P, _P, _I, _I, _I, _P, _P, _P, _P]),
     "gsplat_density_plan": (_I, [_I] + [_P] * 5 + [_I] * 5 + [_F] * 6 + [_P, _SZ, _P]),
     "gsplat_density_apply": (_I, [_I] * 4 + [_P, _SZ] + [_P] * 8 + [_I, _F, _P]),
+    "gsplat_rasterize_splat_back": (_I, [_I] * 5 + [_P] * 8),
+    "gsplat_adam_step_rows": (_I, [_I, _P, _P, _P, _P, _P, _P, _I, _F, _F, _F, _I64, _P, _P,
+                                   _P]),
 }
 
 # the test library's extra entries (include/gsplat_mi355x.h "test hooks", GSPLAT_TEST_HOOKS)

@@ -952,6 +952,135 @@ __global__ __launch_bounds__(256) void raster_fwd3u_kernel(
   clear_side_job();
 }
 
+// ---------------------------------------------------------------- splat-back (forward order)
+// The forward's transpose (gsplat_rasterize_splat_back): every composited (pixel, Gaussian)
+// pair adds its blend weight w = alpha T times the pixel's values to the Gaussian's sums
+// {sum w v_0, sum w v_1, sum w v_2, sum w}.  The walk is raster_fwd3u_kernel's (8x8 blocks, the
+// same staging, cull, sigma / exp helpers, two staged Gaussians per iteration and exits), so
+// every decision is the forward's bit for bit; what the forward keeps per pixel (the colour)
+// is not needed, what it throws away per pair (w) is what is summed.
+//
+// Per iteration the wave needs the 64-lane totals of the two Gaussians' C + 1 values: one
+// halving ladder over the 2 (C + 1) values (reduce_sb, the rungs of common.h reduce18), whose
+// totals one atomic instruction adds from their owning lanes; an iteration in which no lane
+// composited either Gaussian skips both.
+//
+// reduce_sb: l^32 (2 (C + 1) -> C + 1: lanes 0-31 keep the first Gaussian's values, 32-63 the
+// second's), l^16 (-> ceil((C + 1) / 2), the odd slot zero-padded), l^8 (-> 1; a single slot is
+// summed in both lanes of the pair), then the plain sums over 7-l within eight, l^1 and l^2.
+// Each total ends in every lane of a group of eight (C = 1: sixteen); splat_back_slot picks
+// the lowest one.
+template <int C>
+__device__ __forceinline__ float reduce_sb(const float (&v)[2 * (C + 1)]) {
+  constexpr int H = C + 1, Q = (H + 1) / 2;
+  const int lane = __lane_id();
+  float a[H];
+#pragma unroll
+  for (int k = 0; k < H; ++k) a[k] = swap32_sum(v[k], v[k + H]);
+  float b[Q];
+#pragma unroll
+  for (int k = 0; k < Q; ++k) b[k] = swap16_sum(a[2 * k], 2 * k + 1 < H ? a[2 * k + 1] : 0.f);
+  float c;
+  if constexpr (Q == 2) c = dpp_pair_sum<0x128>(b[0], b[1], (lane & 8) != 0);
+  else c = b[0] + dpp_f<0x128>(b[0]);
+  c += dpp_f<0x141>(c);  // row_half_mirror: 7-l within eight
+  c += dpp_f<0xB1>(c);   // quad_perm [1,0,3,2]
+  c += dpp_f<0x4E>(c);   // quad_perm [2,3,0,1]
+  asm volatile("" : "+v"(c));  // (kept fused ahead of the caller's atomic branch)
+  return c;
+}
+// Which of the 2 (C + 1) values reduce_sb() leaves in this lane, for the lowest lane holding
+// each; -1 elsewhere (a probe, like reduce18_slot; the zero pad of C = 2 decodes to -1).
+template <int C>
+__device__ __forceinline__ int splat_back_slot() {
+  const int lane = __lane_id();
+  float p[2 * (C + 1)];
+#pragma unroll
+  for (int k = 0; k < 2 * (C + 1); ++k) p[k] = lane == 0 ? (float)(k + 1) : 0.f;
+  const int cand = (int)reduce_sb<C>(p) - 1;
+  int keep = cand;
+  for (int k = 0; k < 64; ++k)
+    if (k < lane && cand >= 0 && __builtin_amdgcn_readlane(cand, k) == cand) keep = -1;
+  return keep;
+}
+
+template <int C>
+__global__ __launch_bounds__(256) void raster_splat_back_kernel(
+    int tbx, int tby, int H, int W, const int *__restrict__ gids, const int2 *__restrict__ bins,
+    const float2 *__restrict__ xys, const float *__restrict__ conics,
+    const float *__restrict__ opacity, const float *__restrict__ values,
+    float *__restrict__ sums) {
+  const WaveRect R = wave_rect<Block8>(tbx, tby, H, W);
+  if (!R.live) return;  // wave-uniform
+  __shared__ GStage lds[4][64];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int i = R.i0, j = R.j;
+  const float px = (float)j, py = (float)i;
+  // the lane's pixel values, staged once (a lane outside the image never composites)
+  bool done = !(i < H && j < W);
+  float val[C];
+#pragma unroll
+  for (int c = 0; c < C; ++c) val[c] = done ? 0.f : values[((size_t)i * W + j) * C + c];
+  float T = 1.f;
+  // reduce_sb lane roles, learned once: value k = slot (Gaussian slot / (C + 1), field
+  // slot % (C + 1): the channels, then the weight, which lives in sums[g][3])
+  const int slot = splat_back_slot<C>();
+  const bool for0 = slot >= 0 && slot <= C, for1 = slot > C;
+  const int fld = for1 ? slot - (C + 1) : slot;
+  const int field = fld == C ? 3 : fld;
+  const int2 range = bins[R.tile];
+  GStage *stage = lds[__builtin_amdgcn_readfirstlane(wave)];  // (uniform: SGPR address arithmetic)
+  for (int b = range.x; b < range.y; b += 64) {
+    if (__all(done)) break;
+    const int idx = b + lane;
+    GStage s;
+    // (no colours here: the colour slots of the staged record are filled from the conic, three
+    // loads the cull has already issued, and never read)
+    const bool keep = idx < range.y && stage_gaussian(idx, gids, xys, conics, conics, opacity,
+                                                      R.rx0, R.rx1, R.ry0, R.ry1, s);
+    const unsigned long long kmask = __ballot(keep);
+    const int n = __popcll(kmask);
+    if (keep) stage[lanes_below(kmask)] = s;
+    wave_lds_sync();
+    for (int t = 0; t < n; t += 2) {
+      GStage G[2];
+      G[0] = stage_at(stage, t);
+      G[1] = stage_at(stage, min(t + 1, 63));
+      const bool live1 = t + 1 < n;
+      float w[2];
+#pragma unroll
+      for (int u = 0; u < 2; ++u) {
+        const float dx = G[u].x - px;
+        const float sg = gs_sigma(G[u].hc, G[u].b * dx, G[u].ha * dx * dx, G[u].y - py);
+        const float al = fminf(0.999f, G[u].o * gs_vis(sg));
+        const bool v = !done && (u == 0 || live1) && sg >= 0.f && al >= ALPHA_MIN;
+        const float nT = T * (1.f - al);
+        const bool term = v && nT <= 1e-4f, comp = v && !term;
+        done = done || term;
+        w[u] = comp ? al * T : 0.f;
+        T = comp ? nT : T;
+      }
+      const unsigned long long any0 = __builtin_amdgcn_ballot_w64(w[0] != 0.f),
+                               any1 = __builtin_amdgcn_ballot_w64(w[1] != 0.f);
+      if (any0 | any1) {  // (an SGPR test)
+        float m[2 * (C + 1)];
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+#pragma unroll
+          for (int c = 0; c < C; ++c) m[u * (C + 1) + c] = w[u] * val[c];
+          m[u * (C + 1) + C] = w[u];
+        }
+        const float v = reduce_sb<C>(m);
+        const bool act = (for0 && any0) || (for1 && any1);
+        const int g = for1 ? G[1].id : G[0].id;
+        if (act) atomicAdd(sums + ((size_t)g * 4 + field), v);
+      }
+      if (__all(done)) break;
+    }
+    wave_lds_sync();
+  }
+}
+
 // ---------------------------------------------------------------- strip backward, C = 3
 // 16x8 strips: the lane's two pixels (4 rows apart) are one float2 pair, blended branch-free
 // (an invalid pixel gets alpha = vis = 0: T, the colour buffer and every partial sum are
@@ -2007,6 +2136,31 @@ extern "C" int gsplat_rasterize_forward_rgbd(int tile_bounds_x, int tile_bounds_
                     tile_bins, xys, conics, colors, opacity, background};
   launch_fwd<true>(st, b, FwdArgs{out_img, final_Ts, final_idx, depths, out_depth});
   return check_launch("rasterize_forward_rgbd");
+}
+
+extern "C" int gsplat_rasterize_splat_back(int tile_bounds_x, int tile_bounds_y, int img_height,
+                                           int img_width, int channels,
+                                           const int32_t *gaussian_ids_sorted,
+                                           const int32_t *tile_bins, const float *xys,
+                                           const float *conics, const float *opacity,
+                                           const float *values, float *sums, void *stream) {
+  hipStream_t st = (hipStream_t)stream;
+  if (bad_frame(tile_bounds_x, tile_bounds_y, img_height, img_width) || channels < 1 ||
+      channels > 3 || !tile_bins || !values || !sums) {
+    set_error("rasterize_splat_back: bad sizes or NULL buffers (tiles=%dx%d H=%d W=%d C=%d)",
+              tile_bounds_x, tile_bounds_y, img_height, img_width, channels);
+    return 1;
+  }
+  const unsigned grid = cdiv((long long)tile_bounds_x * tile_bounds_y, TILES_PER_BLOCK<Block8>);
+#define SPLAT_BACK(C)                                                                          \
+  hipLaunchKernelGGL(raster_splat_back_kernel<C>, dim3(grid), dim3(256), 0, st, tile_bounds_x, \
+                     tile_bounds_y, img_height, img_width, gaussian_ids_sorted,                \
+                     (const int2 *)tile_bins, (const float2 *)xys, conics, opacity, values, sums)
+  if (channels == 1) SPLAT_BACK(1);
+  else if (channels == 2) SPLAT_BACK(2);
+  else SPLAT_BACK(3);
+#undef SPLAT_BACK
+  return check_launch("rasterize_splat_back");
 }
 
 #ifdef GSPLAT_TEST_HOOKS  // the test library only

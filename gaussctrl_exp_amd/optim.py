@@ -46,12 +46,15 @@ class FusedAdam:
         return st
 
     @torch.no_grad()
-    def step(self, names=None, advance: bool = True):
+    def step(self, names=None, advance: bool = True, rows=None):
         """One Adam update of every group with a gradient -- or only of the groups named in
         `names`, so that a caller can update some groups while other gradients are still
         being reduced (TrainStep).  `advance=False` reuses the current step count: the
         groups of one optimisation step split over several calls share their bias
-        correction, exactly as one call would."""
+        correction, exactly as one call would.  `rows`: a bool / uint8 [N] device mask over the
+        parameters' first dimension; a row whose entry is 0 keeps its parameter and both
+        moments bit for bit (gsplat_adam_step_rows), the others take the usual update.  The
+        step count stays global."""
         live = [(g, g["params"][0]) for g in self.param_groups if g["params"][0].grad is not None
                 and (names is None or g.get("name") in names)]
         if advance:
@@ -71,10 +74,26 @@ class FusedAdam:
             M[k], V[k] = st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr()
             numel[k], lrs[k] = p.numel(), float(g["lr"])
         cast = ctypes.cast
-        _lib.call("gsplat_adam_step", n, cast(P, ctypes.c_void_p), cast(G, ctypes.c_void_p),
-                  cast(M, ctypes.c_void_p), cast(V, ctypes.c_void_p),
-                  cast(numel, ctypes.c_void_p), cast(lrs, ctypes.c_void_p), self.step_count,
-                  self.betas[0], self.betas[1], self.eps, _lib.stream(live[0][1].device))
+        args = (n, cast(P, ctypes.c_void_p), cast(G, ctypes.c_void_p),
+                cast(M, ctypes.c_void_p), cast(V, ctypes.c_void_p),
+                cast(numel, ctypes.c_void_p), cast(lrs, ctypes.c_void_p), self.step_count,
+                self.betas[0], self.betas[1], self.eps)
+        dev = live[0][1].device
+        if rows is None:
+            _lib.call("gsplat_adam_step", *args, _lib.stream(dev))
+            return
+        if rows.dtype not in (torch.bool, torch.uint8) or rows.dim() != 1:
+            raise ValueError("FusedAdam.step: rows must be a bool / uint8 [N] mask")
+        _lib.check_device("FusedAdam.step", rows, live[0][1])
+        num_rows = rows.shape[0]
+        row_elems = (ctypes.c_int64 * n)()
+        for k, (g, p) in enumerate(live):
+            if p.dim() < 1 or p.shape[0] != num_rows:
+                raise ValueError(f"FusedAdam.step: rows has {num_rows} entries, parameter "
+                                 f"{g.get('name', k)} has shape {tuple(p.shape)}")
+            row_elems[k] = p.numel() // num_rows if num_rows else 0
+        _lib.call("gsplat_adam_step_rows", *args, num_rows, cast(row_elems, ctypes.c_void_p),
+                  rows.data_ptr(), _lib.stream(dev))
 
     def fused_spec(self, params):
         """The state a kernel needs to take this optimiser's next step itself

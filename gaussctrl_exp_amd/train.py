@@ -139,7 +139,7 @@ class TrainStep:
                  loss: str = "splatfacto", group=None, api=None,
                  grad_exchange: str = "sh_views", render_mode: str = "caller",
                  fuse_adam: bool = True, sparse_exchange: str = "auto",
-                 density=None, density_seed: int = 0):
+                 density=None, density_seed: int = 0, trainable=None):
         if render_mode not in ("caller", "fused"):
             raise ValueError(f"render_mode must be 'caller' or 'fused', not {render_mode}")
         if render_mode == "fused" and (api is not None or not scene.means.is_cuda):
@@ -149,6 +149,19 @@ class TrainStep:
         # (gc_model.py:158-238, what gc_model.py runs through the drop-in); "fused": the same
         # step with that glue inside the HIP kernels (fused.render_fused)
         self.render_mode = render_mode
+        # trainable: a bool [N] device mask; only its rows are trained, every other Gaussian
+        # keeps its parameters and Adam moments bit for bit (FusedAdam.step(rows=...)).  The
+        # Adam steps fused into other kernels know no rows and are switched off with it.
+        if trainable is not None:
+            if density is not None or api is not None:
+                raise ValueError("TrainStep(trainable=...) cannot be combined with density "
+                                 "control or an api override")
+            if not (torch.is_tensor(trainable) and trainable.dtype == torch.bool and
+                    trainable.is_cuda and tuple(trainable.shape) == (scene.num_points,)):
+                raise ValueError("TrainStep: trainable must be a bool [N] ROCm tensor")
+            trainable = trainable.contiguous()
+            fuse_adam = False
+        self.trainable = trainable
         # single-GPU fused steps take the Adam update inside the backward kernel
         # (gsplat_fused_preprocess_backward_adam): no gradient tensors are written or re-read
         self.fuse_adam = bool(fuse_adam) and render_mode == "fused" and world_size == 1
@@ -255,6 +268,11 @@ class TrainStep:
         scene, self.last_refine = refine(self.scene, self.opt, stats, cfg, step, H, W,
                                          generator=self.density_generator)
         self.rebind(scene)
+
+    def _rows(self):
+        """The optimiser steps' row mask argument (none without `trainable`: torch's Adam of
+        the CPU emulation takes no such argument)."""
+        return {} if self.trainable is None else {"rows": self.trainable}
 
     def _xyz_lr(self):
         t = min(self.step_count / XYZ_MAX_STEPS, 1.0)
@@ -419,7 +437,7 @@ class TrainStep:
         if gs is not None and xc is not None and xc.adam_applied:
             # the SH groups are updated; the geometry all-reduce overlapped the table kernel
             gs.wait()
-            self.opt.step(names=[n for n in PARAM_NAMES if n not in SH_GROUPS])
+            self.opt.step(names=[n for n in PARAM_NAMES if n not in SH_GROUPS], **self._rows())
             self.step_count += 1
             if self.density is not None:
                 self._after_step(self.step_count - 1)
@@ -430,12 +448,13 @@ class TrainStep:
             # the SH-feature gradients (81 % of the update's bytes) are final: update them
             # while the other groups' all-reduces are in flight, then the rest
             works = gs.start()
-            self.opt.step(names=SH_GROUPS)
+            self.opt.step(names=SH_GROUPS, **self._rows())
             gs.finish(works)
-            self.opt.step(names=[n for n in PARAM_NAMES if n not in SH_GROUPS], advance=False)
+            self.opt.step(names=[n for n in PARAM_NAMES if n not in SH_GROUPS], advance=False,
+                          **self._rows())
         else:
             self.sync_grads()
-            self.opt.step()
+            self.opt.step(**self._rows())
         self.step_count += 1
         if self.density is not None:
             self._after_step(self.step_count - 1)

@@ -301,6 +301,25 @@ int gsplat_rasterize_forward_rgbd(int tile_bounds_x, int tile_bounds_y, int img_
                                   const float *background, float *out_img, float *out_depth,
                                   float *final_Ts, int32_t *final_idx, void *stream);
 
+/* Splat-back: the forward's transpose (no gsplat counterpart).  Every pixel walks its tile list
+ * front to back with exactly gsplat_rasterize_forward's decisions (sigma < 0 or alpha =
+ * min(0.999, o exp(-sigma)) < 1/255 skips the pair; the walk stops before T (1 - alpha) <= 1e-4,
+ * the stopping Gaussian is not composited), and every composited (pixel p, Gaussian g) pair adds
+ * its blend weight w = alpha T times the pixel's values to the Gaussian:
+ *   sums[g][c] += w * values[p][c]  (c < channels),   sums[g][3] += w.
+ * values [H,W,channels], 1 <= channels <= 3; sums [N,4] is accumulated into, never cleared: zero
+ * it once and call once per view, then sums[g][0..2] / sums[g][3] is the weighted mean of the
+ * values the Gaussian was blended into (a 2D mask lifted onto the Gaussians) and sums[g][3] its
+ * total visibility.  Takes no colours, background or forward state.  With values = v_output and
+ * alpha_max = 0.999, sums[g][c] equals gsplat_rasterize_backward's v_colors[g][c].
+ * Accumulates with fp32 atomics: sums is NOT bit-reproducible from run to run, and the
+ * deterministic mode (gsplat_set_deterministic) is not honoured here. */
+int gsplat_rasterize_splat_back(int tile_bounds_x, int tile_bounds_y, int img_height,
+                                int img_width, int channels, const int32_t *gaussian_ids_sorted,
+                                const int32_t *tile_bins, const float *xys, const float *conics,
+                                const float *opacity, const float *values, float *sums,
+                                void *stream);
+
 /* v_output [H,W,C], v_output_alpha [H,W] (may be NULL: an all-zero alpha gradient); gradients v_xy [N,2], v_conic [N,3],
  * v_colors [N,C], v_opacity [N] are fully written.  alpha_max is the backward alpha clamp
  * (gsplat 0.1.x uses 0.99f).  workspace holds the per-Gaussian gradient
@@ -636,6 +655,18 @@ int gsplat_adam_step(int num_tensors, float *const *params, const float *const *
                      float *const *exp_avgs, float *const *exp_avg_sqs, const int64_t *numels,
                      const float *lrs, int step, float beta1, float beta2, float eps,
                      void *stream);
+
+/* The same step with frozen rows (training a selection of the Gaussians): every tensor is
+ * [num_rows, row_elems[i]] (row_elems: a HOST array, numels[i] == num_rows * row_elems[i], 0 for
+ * an empty tensor) and rows is a DEVICE byte mask [num_rows].  A row whose byte is 0 keeps its
+ * parameter and both moments bit for bit -- a zero gradient would still move it through the
+ * moments; every other element gets exactly gsplat_adam_step's update, bit-identical to it.
+ * One launch; the step number and its bias corrections are shared by every row. */
+int gsplat_adam_step_rows(int num_tensors, float *const *params, const float *const *grads,
+                          float *const *exp_avgs, float *const *exp_avg_sqs,
+                          const int64_t *numels, const float *lrs, int step, float beta1,
+                          float beta2, float eps, int64_t num_rows, const int64_t *row_elems,
+                          const uint8_t *rows, void *stream);
 
 /* ---- density control (splatfacto's refinement) --------------------------------------------
  * nerfstudio 1.0.0 SplatfactoModel's after_train / refinement_after callbacks, which the
