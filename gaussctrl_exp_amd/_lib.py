@@ -90,6 +90,9 @@ SIGNATURES = {
                                                [_I] * 4 + [_F] + [_P] * 8 + [_SZ, _P]),
     "gsplat_fused_preprocess_forward_part": (_I, [_I, _I, _I, _I] + [_P] * 9 + [_F] * 4 +
                                              [_I] * 4 + [_F] + [_P] * 8 + [_SZ, _P]),
+    "gsplat_fused_preprocess_forward_views": (_I, [_I] * 4 + [_P] * 7 + [_I] * 4 + [_F] +
+                                              [_P] * 8 + [_SZ, _P]),
+    "gsplat_rasterize_forward_rgbd_views": (_I, [_I] * 6 + [_P] * 14),
     "gsplat_bin_count_keyed": (_I, [_I, _I, _I, _P, _P, _SZ, _P]),
     "gsplat_bin_count_keyed_ex": (_I, [_I, _I, _I, _P, _P, _SZ, _c.c_uint32, _P]),
     "gsplat_bin_speculative": (_I, [_I, _I64, _I, _I, _P, _P, _SZ, _c.c_uint32, _P, _P, _P, _SZ,

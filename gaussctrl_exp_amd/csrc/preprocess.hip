@@ -306,6 +306,132 @@ __global__ __launch_bounds__(sh_threads(K)) void fused_fwd_sh_kernel(FusedFwdArg
     fused_fwd_body<K, false, 2>(a, pp, smem, g0, cnt);
 }
 
+// ---- the forward of a batch of views (gsplat_fused_preprocess_forward_views) ----------------
+// The eval render of V cameras of one scene: a Gaussian's raw parameters are loaded, its
+// features_rest row staged in LDS and its activations computed ONCE; the projection and the
+// colour then run per view from those registers / that LDS row.  Bytes: the single-view
+// kernel's (92 + 12 K) N are (44 + 12 K) N of parameters (means 12, scales 12, quats 16,
+// opacity 4, features 12 K) and 48 N of outputs, plus 24 N of binning inputs when binned.  Here
+// the parameters are read once and opacity written once, (48 + 12 K) N, plus per view 68 B per
+// row, culled rows included (xys 8, depths 4, radii 4, conics 12, num_tiles_hit 4, colours 12,
+// the binning's key 4 + val 4 + record 16): (48 + 12 K) N + 68 V N, against
+// V (116 + 12 K) N for V single binned calls.
+//
+// The camera table (device, GSPLAT_VIEW_CAM_FLOATS = 48 floats per view, read with uniform
+// scalar loads like load_cam_scalar): [0,16) viewmat (rows 0..2 used), [16,32) projmat,
+// [32,35) campos, [35,39) fx fy cx cy, [39,48) padding.  tan_fov is formed per view exactly
+// as make_proj_params forms it on the host (a double division, IEEE on the device too).
+//
+// Row v N + g of every per-view output is bit for bit what gsplat_fused_preprocess_forward_
+// binned writes at row g for camera v: the same functions on the same values.  The binning
+// inputs describe V N points on a grid of tbx x (V tby) tiles: view v's tile rows are
+// [v tby, (v + 1) tby), its bounding box clamped to its own tby BEFORE the offset.
+constexpr int VIEW_CAM_FLOATS = GSPLAT_VIEW_CAM_FLOATS;
+static_assert(VIEW_CAM_FLOATS >= 39, "viewmat 16 + projmat 16 + campos 3 + fx fy cx cy");
+
+struct FusedViewsArgs {
+  int n, degrees_to_use, views;
+  const float *means, *log_scales, *quats, *opacity_logits, *features_dc, *features_rest;
+  const float *cams;  // [views, VIEW_CAM_FLOATS]
+  float *xys, *depths;
+  int *radii;
+  float *conics;
+  int *num_tiles_hit;
+  float *colors;   // the six above: [views * n] rows
+  float *opacity;  // [n]
+  BinKeys bin;     // of views * n points
+};
+
+template <int K>
+__global__ __launch_bounds__(sh_threads(K)) void fused_fwd_views_kernel(FusedViewsArgs a,
+                                                                        ProjParams shared) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  typedef __attribute__((address_space(4))) const float cfloat;
+  constexpr int RROW = (K - 1) * 3;
+  constexpr int RP = RROW | 1;
+  constexpr int THR = sh_threads(K);
+  const long long g0 = (long long)blockIdx.x * THR;
+  const int cnt = (int)min((long long)THR, (long long)a.n - g0);
+  const int t = threadIdx.x;
+  const bool live = t < cnt;
+  const long long g = g0 + (live ? t : 0);
+  const float p0 = a.means[3 * g], p1 = a.means[3 * g + 1], p2 = a.means[3 * g + 2];
+  float lsv[3], qv[4], dc[3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) lsv[k] = a.log_scales[3 * g + k];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) qv[k] = a.quats[4 * g + k];
+  const float ologit = a.opacity_logits[g];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) dc[c] = a.features_dc[3 * g + c];
+  if constexpr (K > 1) {
+    stage_rows<RROW, RP, THR>(a.features_rest + g0 * RROW, cnt, smem);
+    __syncthreads();  // (the kernel's only barrier: a thread past the block's count leaves next)
+  }
+  if (!live) return;
+  float s[3], qr[4], qn[4], norm;
+  activate_vals(lsv, qv, s, qr, qn, norm);
+  a.opacity[g] = sigmoidf(ologit);  // gc_model.py:215
+  float flat[3] = {0.f, 0.f, 0.f};  // K == 1: sigmoid(features_dc), the same in every view
+  if constexpr (K == 1) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) flat[c] = sigmoidf(dc[c]);
+  }
+  for (int v = 0; v < a.views; ++v) {  // (uniform)
+    const float *ct = a.cams + (size_t)v * VIEW_CAM_FLOATS;
+    Cam cam;
+    load_cam_scalar(cam, ct, ct + 16);
+    cfloat *in = (cfloat *)(ct + 35);
+    ProjParams pp = shared;
+    pp.fx = in[0];
+    pp.fy = in[1];
+    pp.cx = in[2];
+    pp.cy = in[3];
+    pp.tan_fovx = (float)(0.5 * (double)pp.W / (double)pp.fx);  // make_proj_params'
+    pp.tan_fovy = (float)(0.5 * (double)pp.H / (double)pp.fy);
+    ProjOut o;
+    project_one(cam, pp, p0, p1, p2, s[0], s[1], s[2], qn[0], qn[1], qn[2], qn[3], o);
+    const long long r = (long long)v * a.n + g;
+    a.xys[2 * r] = o.xy[0];
+    a.xys[2 * r + 1] = o.xy[1];
+    a.depths[r] = o.depth;
+    a.radii[r] = o.radius;
+    a.conics[3 * r] = o.con[0];
+    a.conics[3 * r + 1] = o.con[1];
+    a.conics[3 * r + 2] = o.con[2];
+    a.num_tiles_hit[r] = o.tiles;
+    {  // fused_fwd_body's binning inputs, on the stacked grid
+      const bool vis = o.radius > 0;
+      a.bin.keys[r] = vis ? __float_as_uint(o.depth) : 0xFFFFFFFFu;
+      a.bin.vals[r] = (uint32_t)r;
+      const int c = vis ? o.tiles : 0;
+      uint4 q = {c > 0 ? (uint32_t)c : 0u, 0u, 0u, 0u};
+      if (c > 0) {
+        int x0, x1, y0, y1;
+        tile_bbox(o.xy[0], o.xy[1], (float)o.radius, pp.tbx, pp.tby, x0, x1, y0, y1);
+        const int row0 = v * pp.tby;  // (views * tby <= 65,535: checked by the entry)
+        q.y = (uint32_t)x0 | ((uint32_t)(y0 + row0) << 16);
+        q.z = (uint32_t)x1 | ((uint32_t)(y1 + row0) << 16);
+      }
+      a.bin.rec[r] = q;
+    }
+    if constexpr (K == 1) {
+#pragma unroll
+      for (int c = 0; c < 3; ++c) a.colors[3 * r + c] = flat[c];
+    } else {
+      float b[25];
+      const int nb = view_basis(a.degrees_to_use, p0, p1, p2, ct + 32, b);
+      const float *row = smem + t * RP;
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        const float val =
+            sh_channel<K>(b, nb, [&](int k) { return k == 0 ? dc[c] : row[(k - 1) * 3 + c]; });
+        a.colors[3 * r + c] = clamp0_signed(val + 0.5f);  // gc_model.py:201
+      }
+    }
+  }
+}
+
 template <int K, bool ADAM = false>
 __global__ __launch_bounds__(sh_threads(K)) void fused_bwd_kernel(FusedBwdArgs a, ProjParams pp,
                                                                   FusedAdamArgs o = {}) {
@@ -638,6 +764,52 @@ extern "C" int gsplat_fused_preprocess_forward_part(
                             clip_thresh, xys, depths, radii, conics, num_tiles_hit, colors,
                             opacity, nullptr, nullptr, nullptr, part == 1 ? bin_workspace : nullptr,
                             bin_workspace_bytes, stream, part);
+}
+
+extern "C" int gsplat_fused_preprocess_forward_views(
+    int num_points, int sh_bases, int degrees_to_use, int num_views, const float *means3d,
+    const float *log_scales, const float *quats, const float *opacity_logits,
+    const float *features_dc, const float *features_rest, const float *view_cams,
+    int img_height, int img_width, int tile_bounds_x, int tile_bounds_y, float clip_thresh,
+    float *xys, float *depths, int32_t *radii, float *conics, int32_t *num_tiles_hit,
+    float *colors, float *opacity, void *bin_workspace, size_t bin_workspace_bytes,
+    void *stream) {
+  const int K = sh_bases;
+  const long long rows = (long long)num_views * num_points;
+  if (num_points < 0 || num_views < 1 || !valid_bases(K) || degrees_to_use < 0 ||
+      degrees_to_use > degree_of(K) || img_height <= 0 || img_width <= 0 ||
+      tile_bounds_x <= 0 || tile_bounds_y <= 0 || tile_bounds_x > 65535 ||
+      (long long)num_views * tile_bounds_y > 65535 || rows > 0x7FFFFFFFLL || !view_cams ||
+      !bin_workspace ||
+      (num_points > 0 && (!means3d || !log_scales || !quats || !opacity_logits || !features_dc ||
+                          (K > 1 && !features_rest) || !xys || !depths || !radii || !conics ||
+                          !num_tiles_hit || !colors || !opacity))) {
+    set_error("fused_preprocess_forward_views: bad args (N=%d views=%d sh_bases=%d "
+              "degrees_to_use=%d H=%d W=%d tiles=%dx%d per view; views * N must fit int, "
+              "views * tile rows 16 bits)", num_points, num_views, sh_bases, degrees_to_use,
+              img_height, img_width, tile_bounds_x, tile_bounds_y);
+    return 1;
+  }
+  if (num_points == 0) return 0;
+  FusedViewsArgs args{num_points, degrees_to_use, num_views, means3d, log_scales, quats,
+                      opacity_logits, features_dc, features_rest, view_cams, xys, depths, radii,
+                      conics, num_tiles_hit, colors, opacity,
+                      bin_keys_view(bin_workspace, (int)rows)};
+  if (bin_workspace_bytes < args.bin.bytes) {
+    set_error("fused_preprocess_forward_views: binning workspace %zu < %zu bytes (the "
+              "gsplat_bin_count workspace of views * N points)", bin_workspace_bytes,
+              args.bin.bytes);
+    return 1;
+  }
+  // the intrinsics (and tan_fov) are the kernel's, per view, from the table
+  const ProjParams pp = make_proj_params(1.f, 1.f, 0.f, 0.f, 1.f, clip_thresh, img_height,
+                                         img_width, tile_bounds_x, tile_bounds_y);
+  const int thr = sh_threads(K);
+  const dim3 grid(cdiv(num_points, thr));
+  const size_t smem = K > 1 ? (size_t)thr * (((K - 1) * 3) | 1) * sizeof(float) : 0;
+  hipStream_t st = (hipStream_t)stream;
+  FUSED_DISPATCH(fused_fwd_views_kernel, args);
+  return check_launch("fused_preprocess_forward_views");
 }
 
 static int fused_backward_impl(

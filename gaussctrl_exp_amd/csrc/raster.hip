@@ -284,7 +284,8 @@ __device__ __forceinline__ uint32_t lanes_below(unsigned long long mask) {
 // AND colour -- is issued at once, so staging costs two dependent memory round trips (id,
 // then the rest) instead of four (id, opacity, conic + mean, then the colour of the kept
 // ones); the empty asm makes the colour a use before the keep branch, so the compiler cannot
-// sink its load into that branch.
+// sink its load into that branch.  obase (here and in raw_load): the id's offset into opacity,
+// the one array a batch of views keeps per Gaussian (VIEWS: id - view * N), 0 otherwise.
 //
 // EAGER = false (the forward kernels): the branchy cull and the colour loaded only for kept
 // Gaussians -- the forward's 8x8 blocks keep few of the staged ones, and the eager form's
@@ -296,11 +297,12 @@ __device__ __forceinline__ bool stage_gaussian(int idx, const int *__restrict__ 
                                                const float *__restrict__ conics,
                                                const float *__restrict__ colors,
                                                const float *__restrict__ opacity, float rx0,
-                                               float rx1, float ry0, float ry1, GStage &s) {
+                                               float rx1, float ry0, float ry1, GStage &s,
+                                               int obase = 0) {
   const int g = gids[idx];
   const float2 xy = xys[g];
   const float a = conics[3 * g], b = conics[3 * g + 1], c = conics[3 * g + 2];
-  const float o = opacity[g];
+  const float o = opacity[g - obase];
   if constexpr (!EAGER) {
     const bool keep = touches_rect(xy.x, xy.y, a, b, c, o, rx0, rx1, ry0, ry1);
     if (keep) {
@@ -351,13 +353,13 @@ struct RawG {
 __device__ __forceinline__ RawG raw_load(int g, const float2 *__restrict__ xys,
                                          const float *__restrict__ conics,
                                          const float *__restrict__ colors,
-                                         const float *__restrict__ opacity) {
+                                         const float *__restrict__ opacity, int obase = 0) {
   RawG q;
   q.xy = xys[g];
   q.a = conics[3 * g];
   q.b = conics[3 * g + 1];
   q.c = conics[3 * g + 2];
-  q.o = opacity[g];
+  q.o = opacity[g - obase];
   q.r = colors[3 * g];
   q.g = colors[3 * g + 1];
   q.bl = colors[3 * g + 2];
@@ -766,7 +768,24 @@ __device__ __forceinline__ void upstream_rgb(const L1Grad &l1, const float *__re
 // depth, accumulated with the same weight as the colour channels into out_depth -- exactly
 // channel 0 of a second render with colours = depth and a zero background (gc_model.py:
 // 225-238), without the second binning and traversal.
-template <bool DEPTH = false, bool CNT = false, bool PF = false>
+//
+// VIEWS (with DEPTH: gsplat_rasterize_forward_rgbd_views): the grid covers vb.views frames of
+// tbx x tby tiles stacked along y.  A wave's stacked tile t gives view = t / (tbx tby) and the
+// view's own tile, from which the rectangle, px / py, the cull and the pixel index follow as in
+// a single frame: every pixel sees the single-view operation sequence.  The lists (bins[t]) hold
+// virtual ids view * N + g, which index the per-view arrays; opacity is per Gaussian (obase).
+// The outputs go to the view's slice, with gc_model's eval epilogue per pixel (eval_depth);
+// final_Ts / final_idx (positions in the stacked lists) are written only when given.
+struct ViewBatch {
+  int views = 1, n = 0;       // frames in the batch; Gaussians per view
+  float *out_alpha = nullptr;  // [views, H, W]
+};
+// gc_model.py:222-238 on one pixel, as torch rounds it: rgb = clamp(c + T bg, max=1) (a NaN
+// stays), alpha = 1 - T, depth = d / alpha where alpha > 0 (IEEE division), 1000 where alpha == 0.
+__device__ __forceinline__ float eval_depth(float d, float alpha) {
+  return alpha > 0.f ? d / alpha : (alpha == 0.f ? 1000.f : d);
+}
+template <bool DEPTH = false, bool CNT = false, bool PF = false, bool VIEWS = false>
 __global__ __launch_bounds__(256) void raster_fwd3u_kernel(
     int tbx, int tby, int H, int W, const int *__restrict__ gids, const int2 *__restrict__ bins,
     const float2 *__restrict__ xys, const float *__restrict__ conics,
@@ -776,7 +795,8 @@ __global__ __launch_bounds__(256) void raster_fwd3u_kernel(
     const float *__restrict__ depths, float *__restrict__ out_depth, float4 *__restrict__ zero,
     long long zero_n, const int *__restrict__ zero_radii, int *__restrict__ tile_last,
     unsigned long long *__restrict__ kbits, long long kbw, const float *__restrict__ l1_gt,
-    float *__restrict__ l1_part, int l1_clamp) {
+    float *__restrict__ l1_part, int l1_clamp, ViewBatch vb) {
+  static_assert(!VIEWS || (DEPTH && !CNT), "the batch of views is the RGB+depth eval render");
   // Side job: clear a buffer (the fused path's gradient records) with the memory bandwidth the
   // VALU-bound blend leaves idle -- a grid-stride sweep of coalesced 16-B stores, issued by each
   // wave as it finishes (issued first, the blend's first load wait would also wait for them:
@@ -788,7 +808,15 @@ __global__ __launch_bounds__(256) void raster_fwd3u_kernel(
         zero[k] = make_float4(0.f, 0.f, 0.f, 0.f);
   };
   const WaveLog wlog;
-  const WaveRect R = wave_rect<Block8>(tbx, tby, H, W);
+  // VIEWS: the stacked tile (the list's), its view, and the rectangle of the view's own tile
+  int view = 0, stacked = -1;
+  if constexpr (VIEWS) {
+    stacked = wave_slot<Block8>();
+    view = stacked / (tbx * tby);
+  }
+  WaveRect Rw = wave_rect<Block8>(tbx, tby, H, W, VIEWS ? stacked - view * (tbx * tby) : -1);
+  if constexpr (VIEWS) Rw.live = Rw.live && view < vb.views;
+  const WaveRect R = Rw;
   // tile_last (the list-split plan's walk table, see split_work_kernel): per wave of a tile,
   // the largest final index of its pixels (-1: none in the image)
   constexpr int PXL = Block8::PXL, LROWS = LANE_ROWS<Block8>, WPT = WAVES_PER_TILE<Block8>;
@@ -820,13 +848,14 @@ __global__ __launch_bounds__(256) void raster_fwd3u_kernel(
     cur[k] = 0;
     done[k] = !(i < H && j < W);
   }
-  const int2 range = bins[tile];
+  const int2 range = bins[VIEWS ? stacked : tile];
+  const int obase = VIEWS ? view * vb.n : 0;  // virtual id -> opacity row
   GStage *stage = lds[__builtin_amdgcn_readfirstlane(wave)];  // (uniform: SGPR address arithmetic)
   unsigned c_slots = 0, c_live = 0, c_valid = 0;  // (CNT only)
   StagePipe pipe{};  // (PF: see RawG)
   if (PF && range.x < range.y) {
     pipe.g_next = gids[min(range.x + lane, range.y - 1)];
-    pipe.r_next = raw_load(pipe.g_next, xys, conics, colors, opacity);
+    pipe.r_next = raw_load(pipe.g_next, xys, conics, colors, opacity, obase);
     pipe.g_after = gids[min(range.x + 64 + lane, range.y - 1)];
   }
   // the backward's keep bits (see KeepSrc): one word per staged batch, each stored when the
@@ -849,12 +878,12 @@ __global__ __launch_bounds__(256) void raster_fwd3u_kernel(
       const RawG q = pipe.r_next;
       // the next batch's data and the one after's ids (clamped into the list: unused past it)
       pipe.g_next = pipe.g_after;
-      pipe.r_next = raw_load(pipe.g_next, xys, conics, colors, opacity);
+      pipe.r_next = raw_load(pipe.g_next, xys, conics, colors, opacity, obase);
       pipe.g_after = gids[min(b + 128 + lane, range.y - 1)];
       keep = stage_raw(q, idx < range.y, idx, g, rx0, rx1, ry0, ry1, s);
     } else {
-      keep = idx < range.y &&
-             stage_gaussian(idx, gids, xys, conics, colors, opacity, rx0, rx1, ry0, ry1, s);
+      keep = idx < range.y && stage_gaussian(idx, gids, xys, conics, colors, opacity, rx0, rx1,
+                                             ry0, ry1, s, obase);
     }
     if (DEPTH && keep) s.d = depths[s.id];
     const unsigned long long kmask = __ballot(keep);
@@ -910,10 +939,34 @@ __global__ __launch_bounds__(256) void raster_fwd3u_kernel(
     wave_lds_sync();
   }
   if (kbits && kb_at >= 0 && lane == 0) kbits[kb_at] = kb_word;
+  float *out_alpha = nullptr;
+  if constexpr (VIEWS) {  // the view's slices (wave-uniform offsets: scalar pointer arithmetic)
+    const long long frame = (long long)view * H * W;
+    background += 3 * view;  // [views, 3]
+    out_img += 3 * frame;
+    out_depth += frame;
+    out_alpha = vb.out_alpha + frame;
+    if (final_Ts) final_Ts += frame;
+    if (final_idx) final_idx += frame;
+  }
   const float bg0 = background[0], bg1 = background[1], bg2 = background[2];
 #pragma unroll
   for (int k = 0; k < PXL; ++k) {
     const int i = i0 + LROWS * k;
+    if constexpr (VIEWS) {
+      if (i < H && j < W) {
+        const int pix = i * W + j;
+        const float alpha = 1.f - T[k];
+        if (final_Ts) final_Ts[pix] = T[k];
+        if (final_idx) final_idx[pix] = cur[k];
+        out_img[3 * pix] = l1_clampv(cr[k] + T[k] * bg0, 1);
+        out_img[3 * pix + 1] = l1_clampv(cg[k] + T[k] * bg1, 1);
+        out_img[3 * pix + 2] = l1_clampv(cb[k] + T[k] * bg2, 1);
+        out_alpha[pix] = alpha;
+        out_depth[pix] = eval_depth(cd[k] + T[k] * 0.f, alpha);
+      }
+      continue;
+    }
     if (i < H && j < W) {
       const int pix = i * W + j;
       final_Ts[pix] = T[k];
@@ -2072,21 +2125,24 @@ constexpr bool fwd_variant(bool depth, bool cnt) { return !(depth && cnt); }
 
 // The C = 3 forward: 8x8 blocks (CNT: the lane-slot counting instantiation, same arithmetic;
 // PF: staging pipelined one batch ahead), with f's optional jobs.
-template <bool DEPTH>
-static void launch_fwd(hipStream_t st, const BlendArgs &b, const FwdArgs &f) {
-  const unsigned grid = cdiv(b.tiles(), TILES_PER_BLOCK<Block8>);
+// VIEWS: vb.views frames of b's tile grid stacked along y (b.bins and b.gids are the stacked
+// binning's); the staging is pipelined by the stacked tile count.
+template <bool DEPTH, bool VIEWS = false>
+static void launch_fwd(hipStream_t st, const BlendArgs &b, const FwdArgs &f,
+                       const ViewBatch &vb = ViewBatch{}) {
+  const unsigned grid = cdiv(b.tiles() * vb.views, TILES_PER_BLOCK<Block8>);
   with_flags(
       [&](auto cnt, auto pf) {
         constexpr bool CNT = decltype(cnt)::value, PF = decltype(pf)::value;
         if constexpr (fwd_variant(DEPTH, CNT))
-          hipLaunchKernelGGL((raster_fwd3u_kernel<DEPTH, CNT, PF>), dim3(grid),
+          hipLaunchKernelGGL((raster_fwd3u_kernel<DEPTH, CNT, PF, VIEWS>), dim3(grid),
                              dim3(256), 0, st, b.tbx, b.tby, b.H, b.W, b.gids,
                              (const int2 *)b.bins, (const float2 *)b.xys, b.conics, b.colors,
                              b.opacity, b.background, f.out_img, f.final_Ts, f.final_idx,
                              f.depths, f.out_depth, f.zero, f.zero_n, f.zero_radii, f.tile_last,
-                             f.kbits, f.kbw, f.l1_gt, f.l1_part, f.l1_clamp);
+                             f.kbits, f.kbw, f.l1_gt, f.l1_part, f.l1_clamp, vb);
       },
-      !DEPTH && g_pair_count_on, pipelined_staging(b.tbx, b.tby));
+      !DEPTH && g_pair_count_on, pipelined_staging(b.tbx, b.tby * vb.views));
 }
 
 extern "C" int gsplat_rasterize_forward(int tile_bounds_x, int tile_bounds_y, int img_height,
@@ -2136,6 +2192,34 @@ extern "C" int gsplat_rasterize_forward_rgbd(int tile_bounds_x, int tile_bounds_
                     tile_bins, xys, conics, colors, opacity, background};
   launch_fwd<true>(st, b, FwdArgs{out_img, final_Ts, final_idx, depths, out_depth});
   return check_launch("rasterize_forward_rgbd");
+}
+
+extern "C" int gsplat_rasterize_forward_rgbd_views(
+    int num_views, int num_points, int tile_bounds_x, int tile_bounds_y, int img_height,
+    int img_width, const int32_t *gaussian_ids_sorted, const int32_t *tile_bins,
+    const float *xys, const float *conics, const float *colors, const float *depths,
+    const float *opacity, const float *backgrounds, float *out_img, float *out_depth,
+    float *out_alpha, float *final_Ts, int32_t *final_idx, void *stream) {
+  hipStream_t st = (hipStream_t)stream;
+  const long long tiles = (long long)tile_bounds_x * tile_bounds_y;
+  if (bad_frame(tile_bounds_x, tile_bounds_y, img_height, img_width) || num_views < 1 ||
+      num_points < 0 || (long long)num_views * num_points > 0x7FFFFFFFLL ||
+      (long long)num_views * tiles > 0x7FFFFFFFLL || !gaussian_ids_sorted || !tile_bins ||
+      !xys || !conics || !colors || !depths || !opacity || !backgrounds || !out_img ||
+      !out_depth || !out_alpha) {
+    set_error("rasterize_forward_rgbd_views: bad sizes or NULL buffers (views=%d N=%d "
+              "tiles=%dx%d per view H=%d W=%d; views * N and views * tiles must fit int)",
+              num_views, num_points, tile_bounds_x, tile_bounds_y, img_height, img_width);
+    return 1;
+  }
+  const BlendArgs b{tile_bounds_x, tile_bounds_y, img_height, img_width, gaussian_ids_sorted,
+                    tile_bins, xys, conics, colors, opacity, backgrounds};
+  ViewBatch vb;
+  vb.views = num_views;
+  vb.n = num_points;
+  vb.out_alpha = out_alpha;
+  launch_fwd<true, true>(st, b, FwdArgs{out_img, final_Ts, final_idx, depths, out_depth}, vb);
+  return check_launch("rasterize_forward_rgbd_views");
 }
 
 extern "C" int gsplat_rasterize_splat_back(int tile_bounds_x, int tile_bounds_y, int img_height,

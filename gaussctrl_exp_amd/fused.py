@@ -652,3 +652,156 @@ def render_fused_eval(scene, cam: GCCamera, sh_degree_to_use: int, background: T
     depth_im[alpha > 0] = depth_im[alpha > 0] / alpha[alpha > 0]
     depth_im[alpha == 0] = 1000
     return {"rgb": rgb, "depth": depth_im, "accumulation": alpha, "xys": xys, "radii": radii}
+
+
+# ---- the eval render of a batch of views ------------------------------------------------------
+# floats per view of the device camera table (include/gsplat_mi355x.h GSPLAT_VIEW_CAM_FLOATS):
+# [0,16) viewmat, [16,32) projmat, [32,35) campos, [35,39) fx fy cx cy
+VIEW_CAM_FLOATS = 48
+# render_fused_eval_views' default bound on views-per-chunk x N.  A chunk's rows cost ~68 B of
+# preprocess outputs plus the depth sort's buffers (gsplat_bin_count_workspace_size: ~170 B), and
+# its intersections ~30 B each in the emission: 2^24 rows (16 views of the 1M headline scene)
+# stay within a few GB, and a depth sort of that many keys is still one pass set.
+VIEWS_MAX_POINTS = 1 << 24
+_INT_MAX = 2 ** 31 - 1
+_ROW_FIELD_MAX = 65535  # the binning record's 16-bit tile-row field (common.h BinKeys)
+
+
+def _plan_view_chunks(n: int, tby: int, num_views: int, max_points: Optional[int] = None,
+                      tbx: int = 1):
+    """The view counts of the chunks render_fused_eval_views renders `num_views` views of an
+    `n`-Gaussian scene in (a pure function).  Every chunk of c views satisfies the limits of the
+    stacked binning: c * tby <= 65,535 (the binning record's 16-bit row field), c * n <= INT32_MAX
+    (num_points and the workspace queries are int), tbx * c * tby <= INT32_MAX (gsplat_bin_count /
+    gsplat_bin_emit refuse more tiles; the two binning schemes switch by size on their own), and
+    c * n <= max_points (default VIEWS_MAX_POINTS).  The sizes are balanced (they differ by at
+    most one) and sum to num_views.  ValueError when one view alone breaks a limit."""
+    n, tby, tbx, num_views = int(n), int(tby), int(tbx), int(num_views)
+    if num_views < 1 or n < 0 or tby < 1 or tbx < 1:
+        raise ValueError(f"_plan_view_chunks: bad sizes (n={n} tby={tby} tbx={tbx} "
+                         f"views={num_views})")
+    max_points = VIEWS_MAX_POINTS if max_points is None else int(max_points)
+    if max_points < max(n, 1):
+        raise ValueError(f"render_fused_eval_views: max_points {max_points} < N = {n} "
+                         "(one view must fit a chunk)")
+    most = min(num_views, _ROW_FIELD_MAX // tby, _INT_MAX // (tbx * tby))
+    if n > 0:
+        most = min(most, _INT_MAX // n, max_points // n)
+    if most < 1:
+        raise ValueError(f"render_fused_eval_views: one view ({tbx}x{tby} tiles, N={n}) "
+                         "exceeds the binning's limits")
+    chunks = -(-num_views // most)
+    base, extra = divmod(num_views, chunks)
+    return [base + 1] * extra + [base] * (chunks - extra)
+
+
+def _check_views_args(scene, cams, sh_degree_to_use, background):
+    """render_fused_eval_views' argument checks (ValueError), before any device work."""
+    cams = list(cams)
+    if not cams:
+        raise ValueError("render_fused_eval_views: no cameras")
+    H, W = int(cams[0].height), int(cams[0].width)
+    if H < 1 or W < 1 or any((int(c.height), int(c.width)) != (H, W) for c in cams):
+        raise ValueError("render_fused_eval_views: the views of a batch share one (H, W); got "
+                         f"{sorted({(int(c.height), int(c.width)) for c in cams})}")
+    fr = scene.features_rest
+    K = 1 + fr.shape[1] if fr.dim() == 3 else -1
+    deg = int(sh_degree_to_use)
+    if K not in _DEG_OF_BASES or not 0 <= deg <= _DEG_OF_BASES[K]:
+        raise ValueError(f"render_fused_eval_views: bad SH layout / degree (bases {K}, "
+                         f"degree {sh_degree_to_use})")
+    if not isinstance(background, Tensor) or tuple(background.shape) not in (
+            (3,), (len(cams), 3)):
+        raise ValueError("render_fused_eval_views: background is a tensor [3] or [V, 3] "
+                         f"(V = {len(cams)})")
+    return cams, H, W, K, deg
+
+
+def _view_cam_table(cams, dev) -> Tensor:
+    """The device camera table [V, VIEW_CAM_FLOATS] of gsplat_fused_preprocess_forward_views:
+    one cat of the views' matrices and camera centres, one host copy of the intrinsics (rounded
+    to fp32 as the single-view entry's float arguments are)."""
+    V = len(cams)
+    geo = torch.cat([t for c in cams for t in (
+        c.viewmat.to(device=dev, dtype=torch.float32).reshape(-1)[:12],
+        c.projmat.to(device=dev, dtype=torch.float32).reshape(-1)[:16],
+        c.c2w.to(device=dev, dtype=torch.float32)[..., :3, 3].reshape(3))]).view(V, 31)
+    intr = torch.tensor([[c.fx, c.fy, c.cx, c.cy] for c in cams], dtype=torch.float32)
+    table = torch.zeros((V, VIEW_CAM_FLOATS), device=dev, dtype=torch.float32)
+    table[:, :12] = geo[:, :12]
+    table[:, 16:35] = geo[:, 12:]
+    table[:, 35:39] = intr.to(dev)
+    return table
+
+
+@torch.no_grad()
+def render_fused_eval_views(scene, cams, sh_degree_to_use: int, background: Tensor, *,
+                            max_points: Optional[int] = None, return_state: bool = False):
+    """render_fused_eval for a batch of V cameras of one scene in one pass: one fused preprocess
+    that reads the parameters once and projects / colours them per view
+    (gsplat_fused_preprocess_forward_views), ONE binning of the V N virtual points on the views'
+    tile grids stacked along y (the existing entries, one host read of the intersection count),
+    and one RGB+depth blend over the stacked grid with the eval epilogue -- alpha, depth / alpha,
+    the 1000 fill, the clamp -- per pixel (gsplat_rasterize_forward_rgbd_views).
+
+    cams: a non-empty sequence of GCCamera of one (H, W); the intrinsics may differ.
+    background: [3] or [V, 3].  Returns dict(rgb [V,H,W,3], depth [V,H,W,1], accumulation
+    [V,H,W,1], radii [V,N] int32, xys [V,N,2]); view v of each is bit-identical to
+    render_fused_eval(scene, cams[v], ...), with ONE difference: where that returns depth =
+    accumulation = None for a view that sees nothing, the batch returns the view filled with
+    background / 0 / 1000 (what the blend writes for an empty tile list).
+
+    max_points bounds (views per chunk) x N (default VIEWS_MAX_POINTS); the batch is split into
+    the chunks of _plan_view_chunks, each one pass with one host read.  return_state=True adds
+    "state": per chunk dict(views=(first, end), gaussian_ids_sorted, tile_bins [c tiles, 2] (view
+    v's tiles at (v - first) tiles, ids = (v - first) N + g), num_intersects, blended).
+    No autograd.  ValueError for bad arguments, before any device work."""
+    cams, H, W, K, deg = _check_views_args(scene, cams, sh_degree_to_use, background)
+    V, n = len(cams), scene.means.shape[0]
+    tbx, tby = (W + BLOCK_X - 1) // BLOCK_X, (H + BLOCK_Y - 1) // BLOCK_Y
+    chunks = _plan_view_chunks(n, tby, V, max_points, tbx)
+    params = [_contig_f32(t) for t in (scene.means, scene.scales, scene.quats, scene.opacities,
+                                       scene.features_dc, scene.features_rest)]
+    background = _contig_f32(background)
+    dev = _lib.check_device("render_fused_eval_views", *params, background)
+    bgs = background if background.dim() == 2 else background.expand(V, 3).contiguous()
+    table = _view_cam_table(cams, dev)
+    f32 = dict(device=dev, dtype=torch.float32)
+    i32 = dict(device=dev, dtype=torch.int32)
+    rgb, depth = torch.empty((V, H, W, 3), **f32), torch.empty((V, H, W, 1), **f32)
+    acc = torch.empty((V, H, W, 1), **f32)
+    xys, radii = torch.empty((V, n, 2), **f32), torch.empty((V, n), **i32)
+    opac = torch.empty((n,), **f32)
+    P, st = _lib.ptr, _lib.stream(dev)
+    state, v0 = [], 0
+    for c in chunks:
+        v1, rows = v0 + c, c * n
+        depths, conics = torch.empty((rows,), **f32), torch.empty((rows, 3), **f32)
+        colors, nth = torch.empty((rows, 3), **f32), torch.empty((rows,), **i32)
+        xys_c, radii_c = xys[v0:v1].view(rows, 2), radii[v0:v1].view(rows)
+        ws1 = torch.empty((max(_lib.query("gsplat_bin_count_workspace_size", rows), 1),),
+                          device=dev, dtype=torch.uint8)
+        _lib.call("gsplat_fused_preprocess_forward_views", n, K, deg, c,
+                  *[P(t) for t in params[:5]], P(params[5]) if K > 1 else None, P(table[v0:v1]),
+                  H, W, tbx, tby, 0.01, P(xys_c), P(depths), P(radii_c), P(conics), P(nth),
+                  P(colors), P(opac), P(ws1), ws1.numel(), st)
+        # the stacked grid: c * tby tile rows (bin_gaussians derives them from the height)
+        num_intersects, gids, bins = bin_gaussians(xys_c, depths, radii_c, nth,
+                                                   c * tby * BLOCK_Y, W, keyed_workspace=ws1)
+        if num_intersects >= 1:
+            _lib.call("gsplat_rasterize_forward_rgbd_views", c, n, tbx, tby, H, W, P(gids),
+                      P(bins), P(xys_c), P(conics), P(colors), P(depths), P(opac),
+                      P(bgs[v0:v1]), P(rgb[v0:v1]), P(depth[v0:v1]), P(acc[v0:v1]), None, None,
+                      st)
+        else:  # nothing visible in the whole chunk: what the blend writes for empty lists
+            rgb[v0:v1] = bgs[v0:v1, None, None, :]
+            depth[v0:v1] = 1000.0
+            acc[v0:v1] = 0.0
+        if return_state:
+            state.append({"views": (v0, v1), "gaussian_ids_sorted": gids, "tile_bins": bins,
+                          "num_intersects": num_intersects, "blended": num_intersects >= 1})
+        v0 = v1
+    out = {"rgb": rgb, "depth": depth, "accumulation": acc, "xys": xys, "radii": radii}
+    if return_state:
+        out["state"] = state
+    return out

@@ -301,6 +301,26 @@ int gsplat_rasterize_forward_rgbd(int tile_bounds_x, int tile_bounds_y, int img_
                                   const float *background, float *out_img, float *out_depth,
                                   float *final_Ts, int32_t *final_idx, void *stream);
 
+/* gsplat_rasterize_forward_rgbd over num_views frames in one launch, with gc_model's eval
+ * epilogue (gc_model.py:222-238) per pixel.  The binning is the stacked one of
+ * gsplat_fused_preprocess_forward_views: tile_bins [num_views * tiles, 2] (view v's tiles at
+ * v * tiles), gaussian_ids_sorted of virtual rows v N + g; xys, conics, colors, depths
+ * [num_views * N] rows, opacity [N], backgrounds [num_views, 3]; tile bounds, img_height and
+ * img_width are ONE view's.  Every pixel of view v sees the operation sequence of the
+ * single-view forward on view v's lists.  Outputs [num_views, H, W, .]:
+ *   out_alpha = 1 - T,  out_img = min(c + T background_v, 1) (a NaN stays),
+ *   out_depth = out_alpha > 0 ? (sum depth alpha T) / out_alpha : 1000  (IEEE division)
+ * -- bit for bit torch's clamp(max=1), 1 - final_Ts, and the masked division / fill of the
+ * caller.  A tile with an empty list writes background_v, 0 and 1000.  final_Ts [num_views,H,W]
+ * and final_idx (positions in the stacked list) are optional (NULL: not written).
+ * Limits (status 1): num_views * N and num_views * tiles <= INT32_MAX. */
+int gsplat_rasterize_forward_rgbd_views(
+    int num_views, int num_points, int tile_bounds_x, int tile_bounds_y, int img_height,
+    int img_width, const int32_t *gaussian_ids_sorted, const int32_t *tile_bins,
+    const float *xys, const float *conics, const float *colors, const float *depths,
+    const float *opacity, const float *backgrounds, float *out_img, float *out_depth,
+    float *out_alpha, float *final_Ts, int32_t *final_idx, void *stream);
+
 /* Splat-back: the forward's transpose (no gsplat counterpart).  Every pixel walks its tile list
  * front to back with exactly gsplat_rasterize_forward's decisions (sigma < 0 or alpha =
  * min(0.999, o exp(-sigma)) < 1/255 skips the pair; the walk stops before T (1 - alpha) <= 1e-4,
@@ -442,6 +462,32 @@ int gsplat_fused_preprocess_forward_part(
     const float *log_scales, const float *quats, const float *opacity_logits,
     const float *features_dc, const float *features_rest, const float *viewmat,
     const float *projmat, const float *campos, float fx, float fy, float cx, float cy,
+    int img_height, int img_width, int tile_bounds_x, int tile_bounds_y, float clip_thresh,
+    float *xys, float *depths, int32_t *radii, float *conics, int32_t *num_tiles_hit,
+    float *colors, float *opacity, void *bin_workspace, size_t bin_workspace_bytes,
+    void *stream);
+/* gsplat_fused_preprocess_forward_binned for num_views cameras of one scene in one launch (the
+ * eval render of a batch of views; no gsplat counterpart): every Gaussian's parameters are read
+ * and activated once, then projected and coloured per view.
+ * view_cams [num_views, GSPLAT_VIEW_CAM_FLOATS] (DEVICE), per view: floats [0,16) viewmat (row
+ * major, rows 0..2 read), [16,32) projmat, [32,35) campos, [35,39) fx fy cx cy, the rest
+ * padding.  img_height / img_width, the tile bounds (of ONE view) and clip_thresh are shared.
+ * The per-view outputs have num_views * N rows, view v's Gaussian g at virtual row v N + g:
+ * xys, depths, radii, conics, num_tiles_hit, colors -- each row bit for bit what the binned
+ * forward writes at row g for camera v alone (xys in the view's own pixel coordinates);
+ * opacity [N] once.  bin_workspace (gsplat_bin_count_workspace_size(num_views * N) bytes)
+ * receives the depth-sort inputs of num_views * N points on a grid of tile_bounds_x x
+ * (num_views * tile_bounds_y) tiles: key = depth bits (0xFFFFFFFF culled), val = the virtual row,
+ * record = {tiles, x0 | (y0 + v tby) << 16, x1 | (y1 + v tby) << 16, 0} with the box clamped to
+ * the view's own tile_bounds_y before the offset -- follow it with gsplat_bin_count_keyed /
+ * gsplat_bin_emit at num_points = num_views * N, tile_bounds_y = num_views * tile_bounds_y:
+ * view v's tiles then hold the single-view lists (ids + v N) bit for bit.
+ * Limits (status 1): num_views * N <= INT32_MAX, num_views * tile_bounds_y <= 65,535. */
+#define GSPLAT_VIEW_CAM_FLOATS 48
+int gsplat_fused_preprocess_forward_views(
+    int num_points, int sh_bases, int degrees_to_use, int num_views, const float *means3d,
+    const float *log_scales, const float *quats, const float *opacity_logits,
+    const float *features_dc, const float *features_rest, const float *view_cams,
     int img_height, int img_width, int tile_bounds_x, int tile_bounds_y, float clip_thresh,
     float *xys, float *depths, int32_t *radii, float *conics, int32_t *num_tiles_hit,
     float *colors, float *opacity, void *bin_workspace, size_t bin_workspace_bytes,
